@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the AnatoMask pretraining step on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   N > 1 without a launcher: this process (which has not touched the GPU) starts
       python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py <same flags>
   as a child, one rank per GPU, RCCL gradient all-reduce; under a launcher (RANK/WORLD_SIZE set) it is a rank.
@@ -11,14 +11,24 @@ bf16 MFMA with fp32 accumulation, fp32 master weights + AdamW + EMA; one "step" 
 P/pretrain_AntoMask.py:418-441 (teacher fwd, sampler, student fwd, loss, bwd, clip, AdamW, EMA) on a batch
 of B synthetic N(0,1) volumes already resident in HBM.  value = volumes/s over all ranks (weak scaling).
 
+A plain run sets up, takes W warm-up steps, times exactly K steps, writes the outputs of the last timed step if
+--dump-outputs is given, and prints the JSON line.  Everything else (the fields marked [full] below) is measured
+only with --full; the --no-* switches leave out single parts of it.
+
+--dump-outputs DIR (rank 0): what the last timed step returned to its caller, float32, one DIR/<name>.npy each:
+  loss, grad_norm, mask (the student's hard mask, 0/1), recon_loss (the teacher's per-patch loss that guided the
+  sampler) and rec_loss (the student's per-patch loss).  Inputs, initial weights and mask draws are seeded: the same
+  flags give the same inputs in every run, so two builds can be compared output for output.
+
 Extra fields of the JSON line (besides the driver's contract):
   step_ms_median / step_ms_min      per-step durations from HIP events recorded after every step of the timed window
-  value_with_h2d                    the same K steps fed from pinned host memory through the double-buffered copy stream
+  [full] value_with_h2d             the same K steps fed from pinned host memory through the double-buffered copy stream
                                     (anatomask_amd.data.DeviceFeed; the reference's `inp.to(device, non_blocking=True)`): NOT `value`
-  exchange (N > 1)                  RCCL rank count, gradient bytes per step, step time with the exchange disabled, exposed ms
-  roofline                          dominant kernel (profiles/): isolated launch AND the same launch timed inside the step
-  encoder_fwd_hbm                   north-star figure: student sparse-encoder forward vs the 8 TB/s HBM peak
-  cpu_baseline                      the CPU oracle taking one B=1 step on the host cores (rank 0, N = 1 only)
+  [full] exchange (N > 1)           RCCL rank count, gradient bytes per step, step time with the exchange disabled, exposed ms
+  [full] roofline                   dominant kernel (profiles/): isolated launch AND the same launch timed inside the step
+  [full] encoder_fwd_hbm            north-star figure: student sparse-encoder forward vs the 8 TB/s HBM peak
+  [full] secondary                  the same step at batch 4, the reference recipe in fp32 storage, STUNet-L / STUNet-H
+  [full] cpu_baseline               the CPU oracle taking one B=1 step on the host cores (rank 0, N = 1 only)
 """
 import argparse
 import json
@@ -304,6 +314,16 @@ def timed_window(step, steps, world, dist, dev):
     return dt, per, out
 
 
+def dump_outputs(d, out):
+    """`--dump-outputs DIR`: what the last timed step returned to its caller (trainer.step: loss, grad_norm, mask, recon_loss, rec_loss;
+    the whole arrays: 6 KiB per volume at 128^3) as float32 DIR/<name>.npy."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, v in out.items():
+        if v is not None:
+            np.save(os.path.join(d, name + ".npy"), v.detach().float().cpu().numpy())
+
+
 def dry_run_launch(a):
     """`--dry-run-launch` (CPU, gloo; tests/test_launch.py): the N-rank self-launch AND the rank body's N > 1 plumbing without a GPU.
     Every rank builds the real model (STUNet-S) and the real trainer's gradient-exchange state over host flat buffers; a step is
@@ -372,12 +392,18 @@ def main():
     ap.add_argument("--mask-ratio", type=float, default=0.6)
     ap.add_argument("--recompute", action="store_true")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-h2d", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary lines (batch 4; the reference recipe in fp32 storage)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline window, also measure value_with_h2d, exchange (N > 1), roofline, encoder_fwd_hbm, secondary and cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (float32) as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip roofline and encoder_fwd_hbm")
+    ap.add_argument("--no-h2d", action="store_true", help="with --full: skip value_with_h2d")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary lines (batch 4; the reference recipe in fp32 storage)")
     ap.add_argument("--dry-run-launch", action="store_true", help="CPU/gloo check of the N-rank self-launch (no GPU work)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     from anatomask_amd import launch
     if a.gpus > 1 and not launch.launched():
@@ -417,7 +443,7 @@ def main():
     torch.manual_seed(0)                                            # identical init on every rank (+ broadcast in the trainer)
     model = M.build_spark(kw["dims"], kw["depth"], kw["width"], (a.patch,) * 3, a.mask_ratio, compute_dtype=dtype, recompute=a.recompute)
     sd_cpu = ({k: v.clone() for k, v in model.state_dict().items()}
-              if (rank == 0 and world == 1 and not a.no_cpu_baseline and a.size == "B" and a.patch == 128) else None)
+              if (a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and a.size == "B" and a.patch == 128) else None)
     model = model.to(dev)
     tr = AnatoMaskTrainer(model, lr=1e-4, total_epochs=1000, seed=4321 + rank)
     tr.set_epoch(500)
@@ -447,9 +473,11 @@ def main():
                "value_per_gpu": round(a.batch * a.steps / dt, 4),
                "rank_step_ms": {"min": min(r["step_ms_median"] for r in rr), "median": sorted(r["step_ms_median"] for r in rr)[len(rr) // 2],
                                 "max": max(r["step_ms_median"] for r in rr)}}
+        if a.dump_outputs:                                           # (before anything else overwrites the step's buffers: grad_norm is the trainer's)
+            dump_outputs(a.dump_outputs, out)
 
     # ---- the same steps fed from pinned host memory through the copy stream (reported beside `value`, never as `value`)
-    if not a.no_h2d:
+    if a.full and not a.no_h2d:
         host = x.cpu().pin_memory()
         feed = DeviceFeed(({"data": host} for _ in range(a.steps + 4)), dev)
         for _ in range(2):
@@ -461,7 +489,7 @@ def main():
         del feed, host
 
     # ---- exposed communication: the same window with the gradient exchange switched off (N > 1)
-    if dist_on:
+    if a.full and dist_on:
         tr.distributed = False
         for _ in range(2):
             tr.step(x, epoch=500)
@@ -477,12 +505,12 @@ def main():
         dist.barrier()
         tr.distributed = False
         dist.destroy_process_group()
-    if rank == 0 and not a.no_roofline and a.dtype == "bf16":
+    if a.full and rank == 0 and not a.no_roofline and a.dtype == "bf16":
         res["roofline"] = dominant_kernel_roofline(a.batch, dev, tr if world == 1 else None, x, C=kw["width"] // 8, S=a.patch, size=a.size)
         enc = encoder_forward_hbm(model, x, dev, a.size, a.patch, a.mask_ratio)
         if enc is not None:
             res["encoder_fwd_hbm"] = enc
-    if rank == 0:
+    if a.full and rank == 0:
         del tr, model, x
         torch.cuda.empty_cache()
         if world == 1 and not a.no_secondary and a.size == "B" and a.patch == 128:
@@ -492,6 +520,7 @@ def main():
                 res["cpu_baseline"] = cpu_baseline(sd_cpu, kw)
             except Exception as e:                                   # e.g. host OOM: report, do not fail the bench
                 res["cpu_baseline"] = {"value": None, "unit": "volumes/s", "cores": os.cpu_count(), "kind": "port", "sample": f"failed: {e!r}"}
+    if rank == 0:
         print(json.dumps(res), flush=True)
 
 

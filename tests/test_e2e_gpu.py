@@ -620,7 +620,7 @@ def test_bench_rank_body_rccl_world1():
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", AM_BENCH_FORCE_DIST="1", AM_BENCH_COLLECTIVE_TIMEOUT_S="120")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                         "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
-                        "--batch", "2", "--no-cpu-baseline", "--no-secondary", "--no-h2d"],
+                        "--batch", "2", "--full", "--no-cpu-baseline", "--no-secondary", "--no-h2d"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -635,6 +635,35 @@ def test_bench_rank_body_rccl_world1():
     print("bench.py rank body over RCCL (world 1): %.2f ms/step, %.2f without the exchange, %d collectives, last step exposed %.3f ms"
           % (out["ms_per_step"], ex["ms_per_step_without_exchange"], ex["collectives_per_step"], ex["exposed_ms_last_step"]))
     assert "roofline" in out and out["roofline"]["frac"] > 0.2                                             # (measured after the process group was destroyed)
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """`bench.py --gpus 1` without --full: exactly --steps timed steps, the contract fields, none of the --full measurements; with
+    --dump-outputs the last timed step's outputs land in DIR as float32 .npy files whose loss is the line's final_loss."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env.update(HSA_ENABLE_IPC_MODE_LEGACY="0")
+    d = str(tmp_path / "outputs")
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2",
+                        "--dump-outputs", d], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert out["unit"] == "volumes/s" and out["higher_is_better"] is True and out["dtype"] == "bf16" and out["metric"].startswith("pretrain volumes/sec")
+    assert not {"value_with_h2d", "exchange", "roofline", "encoder_fwd_hbm", "secondary", "cpu_baseline"} & set(out)
+    L = (128 // 16) ** 3
+    want = {"loss": (1,), "grad_norm": (1,), "mask": (2, L), "recon_loss": (2, L), "rec_loss": (2, L)}
+    assert sorted(os.listdir(d)) == sorted(n + ".npy" for n in want)
+    got = {n: np.load(os.path.join(d, n + ".npy")) for n in want}
+    for n, shape in want.items():
+        assert got[n].dtype == np.float32 and got[n].shape == shape and np.isfinite(got[n]).all(), n
+    assert round(float(got["loss"][0]), 5) == out["final_loss"]
+    assert set(np.unique(got["mask"])) <= {0.0, 1.0}
 
 
 def test_nonfinite_step_is_skipped_on_the_device_and_latched():

@@ -2,7 +2,7 @@
 # ONE parametrised GPU-box script (replaces the per-experiment round*_X.sh files):  bash tools/gpu_round.sh TAG STAGE [STAGE ...]
 # Every stage writes under gpurun_out/TAG/.  Stages:
 #   tests [PYTEST_ARGS via AM_PYTEST]   pytest -m gpu (default: whole suite)      smoke      __graft_entry__.smoke()
-#   bench        default bench line                  benchLH    STUNet-L 160^3 / STUNet-H 192^3 lines
+#   bench        full bench line (--full)            benchLH    STUNet-L 160^3 / STUNet-H 192^3 lines
 #   census       tools/conv_census.py 16             shapes     conv_shapes_bench + wgrad_shapes_bench
 #   phases       tools/phase_times.py 16             step       rocprofv3 kernel stats of the step (side stream on / off)
 #   convb        rocprofv3 kernel stats of tools/conv_bench.py (the dominant launch)
@@ -19,10 +19,10 @@ for stage in "$@"; do
     tests) timeout ${AM_PYTEST_TIMEOUT:-3000} python3 -m pytest ${AM_PYTEST:-tests} -m gpu -q -p no:cacheprovider -x ${AM_PYTEST_FLAGS:--s} > $out/pytest.txt 2>&1; echo "pytest rc $?" >> $out/pytest.txt
            grep -v amdgpu.ids $out/pytest.txt | grep -n "passed\|failed\|FAILED\|Error\|rc " | tail -8 ;;
     smoke) timeout 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.txt 2>&1; tail -1 $out/smoke.txt ;;
-    bench) timeout 900 python3 bench.py --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err; head -c 400 $out/bench.json; echo ;;
-    benchq) timeout 600 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-h2d > $out/bench_quick.json 2> $out/bench_quick.err; head -c 300 $out/bench_quick.json; echo ;;
-    benchLH) timeout 900 python3 bench.py --size L --patch 160 --mask-ratio 0.7 --batch 4 --steps 8 --warmup 3 --no-h2d > $out/bench_stunet_L_160_m07_b4.json 2> $out/bench_L.err; head -c 300 $out/bench_stunet_L_160_m07_b4.json; echo
-             timeout 900 python3 bench.py --size H --patch 192 --batch 2 --recompute --steps 5 --warmup 2 --no-h2d > $out/bench_stunet_H_192_recompute_b2.json 2> $out/bench_H.err; head -c 300 $out/bench_stunet_H_192_recompute_b2.json; echo ;;
+    bench) timeout 900 python3 bench.py --steps 20 --warmup 5 --full > $out/bench.json 2> $out/bench.err; head -c 400 $out/bench.json; echo ;;
+    benchq) timeout 600 python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-secondary --no-h2d > $out/bench_quick.json 2> $out/bench_quick.err; head -c 300 $out/bench_quick.json; echo ;;
+    benchLH) timeout 900 python3 bench.py --size L --patch 160 --mask-ratio 0.7 --batch 4 --steps 8 --warmup 3 --full --no-h2d > $out/bench_stunet_L_160_m07_b4.json 2> $out/bench_L.err; head -c 300 $out/bench_stunet_L_160_m07_b4.json; echo
+             timeout 900 python3 bench.py --size H --patch 192 --batch 2 --recompute --steps 5 --warmup 2 --full --no-h2d > $out/bench_stunet_H_192_recompute_b2.json 2> $out/bench_H.err; head -c 300 $out/bench_stunet_H_192_recompute_b2.json; echo ;;
     census) timeout 600 python3 tools/conv_census.py 16 > $out/conv_census.txt 2>&1; tail -1 $out/conv_census.txt ;;
     shapes) timeout 300 python3 tools/conv_shapes_bench.py 16 > $out/conv_shapes_b16.txt 2>&1; timeout 300 python3 tools/wgrad_shapes_bench.py 16 > $out/wgrad_shapes_b16.txt 2>&1 ;;
     phases) timeout 300 python3 tools/phase_times.py 16 > $out/phase_times_b16.txt 2>&1; cat $out/phase_times_b16.txt | grep -v amdgpu.ids | tail -4 ;;

@@ -10,5 +10,5 @@ cd /tmp && export TMPDIR=/tmp
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/step_iso -- python3 $root/tools/step_run.py 16 20 0 > $out/step_iso.log 2>&1
 cd $root
 grep ms/step $out/step_iso.log
-timeout 600 python3 bench.py --steps 20 --warmup 5 --no-h2d > $out/bench.json 2> $out/bench.err; tail -c 600 $out/bench.json
+timeout 600 python3 bench.py --steps 20 --warmup 5 --full --no-h2d > $out/bench.json 2> $out/bench.err; tail -c 600 $out/bench.json
 find $out -name "*_kernel_trace.csv" -size +4M -delete; find $out -name "*.db" -delete
