@@ -230,17 +230,21 @@ class PackCache:
 FUSED_PRENORM = True    # tools/step_ab.py engine.FUSED_PRENORM=1,0: passes without a tape fold norm1 + LeakyReLU into conv2's source staging
 
 
-def _enc_block(W, pk, inp, mask, counts, sp, s: int, b: int, x, keep: bool = True):
+def _enc_block(W, pk, inp, mask, counts, sp, s: int, b: int, x, keep: bool = True, stride: Optional[int] = None, prefix: Optional[str] = None):
     """One BasicResBlock (P/STUNet_head.py:96-103) -> (out, record for backward).
     keep=False (no tape: the EMA teacher, validation, stand-alone forwards): where the kernel exists (the thin level-0 layers, conv_rw.hip)
-    a1 = LReLU(norm1(y1)) is never written -- conv2 applies norm1 + LeakyReLU to y1 while it stages its source rows."""
+    a1 = LReLU(norm1(y1)) is never written -- conv2 applies norm1 + LeakyReLU to y1 while it stages its source rows.
+    stride: of the first block (default: 2 for s > 0, the pretraining encoder); prefix: the block's parameter prefix (default: encoder
+    stage s, block b; any other prefix is a block whose first conv reads x, never the stem).  Stages past 4 (the segmentation network's
+    stride-1 stage 5) run at stage 4's grid."""
     dt = pk.dtype
-    bs = 4 - s
-    p = f"{ENC}.{s}.{b}"
+    bs = 4 - min(s, 4)
+    p = f"{ENC}.{s}.{b}" if prefix is None else f"{prefix}.{b}"
     first = b == 0
-    stride = 2 if (first and s > 0) else 1
+    if stride is None or not first:
+        stride = 2 if (first and s > 0) else 1
     rec_ = {"p": p, "s": s, "b": b, "first": first, "stride": stride, "x": x}
-    if s == 0 and first:
+    if s == 0 and first and prefix is None:
         y1, pt1 = ops.stem_conv_fwd(inp, W[f"{p}.conv1.weight"], W[f"{p}.conv1.bias"], mask, bs, dt, want_partials=True)
     else:
         y1, pt1 = ops.conv3d(CONV_FWD, x, pk.get(W, f"{p}.conv1.weight", False, False), W[f"{p}.conv1.bias"], sp, 3, stride,
@@ -256,7 +260,7 @@ def _enc_block(W, pk, inp, mask, counts, sp, s: int, b: int, x, keep: bool = Tru
         y2, pt2 = ops.conv3d(CONV_FWD, a1, w2, W[f"{p}.conv2.bias"], sp, 3, 1,
                              in_mask=mask, in_bshift=bs, out_mask=mask, out_bshift=bs, want_partials=True)
     st2 = _sparse_norm(y2, mask, bs, counts, W[f"{p}.norm2.weight"], W[f"{p}.norm2.bias"], 1e-5, pt2)
-    if s == 0 and first:      # 1x1 Cin=1 shortcut folded into the apply pass
+    if s == 0 and first and prefix is None:      # 1x1 Cin=1 shortcut folded into the apply pass
         out = ops.norm_apply(y2, st2, ACT_LRELU, mask, bs, stem=(inp, W[f"{p}.conv3.weight"].view(-1), W[f"{p}.conv3.bias"]))
     elif first:
         sc = ops.conv3d(CONV_FWD, x, pk.get(W, f"{p}.conv3.weight", False, False), W[f"{p}.conv3.bias"], sp, 1, stride,
@@ -674,3 +678,61 @@ def backward(spec: Spec, W: Dict[str, torch.Tensor], G: Dict[str, torch.Tensor],
         encoder_backward(spec, W, G, pk, inp, mask, tape, dfeat, after_group)
     finally:
         _join_side(inp.device)            # (also when backward raises: the kept activations must not outlive the call)
+
+
+# ====================================================================================== segmentation network (inference only)
+NET = ENC.rsplit(".", 1)[0]            # the STUNet's own parameter names live under this prefix in W (as a stand-alone STUNet's do)
+
+
+def _dense_mask(size: Tuple[int, int, int], device) -> MaskInfo:
+    """all-active patch mask of ONE sample: the dense forward of STUNet.forward with _cur_active None (modules.py)."""
+    f = tuple(v // 16 for v in size)
+    return MaskInfo(torch.ones(1, *f, dtype=torch.uint8, device=device), n_active=f[0] * f[1] * f[2])
+
+
+def seg_encoder_forward(W, pk: PackCache, inp: torch.Tensor, depth: Sequence[int], mask: Optional[MaskInfo] = None, counts=None) -> List[torch.Tensor]:
+    """conv_blocks_context of P/STUNet.py:35-46,72-77 on ONE sample (inp fp32 [1,D,H,W]): the 6 stage maps, channels-last, dense.
+    Stages 0-4 are the pretraining encoder's blocks on an all-active mask; stage 5 is a stride-1 first block with a 1x1 shortcut
+    (pool [1,1,1]) at stage 4's grid.  nn.InstanceNorm3d normalises per sample, hence one sample per call."""
+    size = tuple(inp.shape[1:])
+    if mask is None:
+        mask = _dense_mask(size, inp.device)
+        counts = _counts(mask, range(5))
+    feats, x = [], None
+    for s in range(6):
+        sp = tuple(v >> min(s, 4) for v in size)
+        for b in range(depth[s]):
+            x, _ = _enc_block(W, pk, inp, mask, counts, sp, s, b, x, keep=False, stride=1 if s == 5 else None)
+        feats.append(x)
+    return feats
+
+
+def seg_forward(W, pk: PackCache, inp: torch.Tensor, depth: Sequence[int], all_levels: bool = False) -> List[torch.Tensor]:
+    """P/STUNet.py:70-93 without the heads, forward only (no tape): inp fp32 [B,D,H,W] -> the decoder's output features channels-last
+    [B,D',H',W',C] in the compute dtype, of the last level only or (all_levels) of levels 0..4 (coarse -> fine).
+    Per decoder level u: Upsample_Layer_nearest's 1x1 conv at the COARSE grid (it commutes with nearest upsampling: 1/8 of the work at
+    factor 2) -> am_seg_upcat (upsample into the first half of torch.cat((x, skip), 1)) -> BasicResBlock(s) 2C -> C with a 1x1 shortcut.
+    Samples run one at a time (per-sample InstanceNorm statistics) into batch-shaped outputs."""
+    B = inp.shape[0]
+    outs: List[Optional[torch.Tensor]] = [None] * 5
+    mask = _dense_mask(tuple(inp.shape[1:]), inp.device)
+    counts = _counts(mask, range(5))
+    for bi in range(B):
+        feats = seg_encoder_forward(W, pk, inp[bi:bi + 1], depth, mask, counts)
+        x = feats[5]
+        for u in range(5):
+            s = 4 - u
+            skip = feats[s]
+            sp = tuple(skip.shape[1:4])
+            wn = f"{NET}.upsample_layers.{u}.conv.weight"
+            xu = ops.conv3d(CONV_FWD, x, pk.get(W, wn, False, False), W[f"{NET}.upsample_layers.{u}.conv.bias"], tuple(x.shape[1:4]), 1, 1)
+            x = ops.seg_upcat(xu, skip)
+            for b in range(depth[s]):
+                x, _ = _enc_block(W, pk, None, mask, counts, sp, s, b, x, keep=False, stride=1, prefix=f"{NET}.conv_blocks_localization.{u}")
+            if (all_levels or u == 4) and B == 1:
+                outs[u] = x
+            elif all_levels or u == 4:
+                if outs[u] is None:
+                    outs[u] = torch.empty(B, *x.shape[1:], device=x.device, dtype=x.dtype)
+                outs[u][bi:bi + 1].copy_(x)
+    return outs if all_levels else [outs[4]]

@@ -700,3 +700,72 @@ def resample_affine(src: torch.Tensor, dst: torch.Tensor, affine_3x4, order: int
     arr = (_ct.c_float * 12)(*[float(v) for v in affine_3x4])
     hip.lib().resample_affine(src.data_ptr(), *src.shape, dst.data_ptr(), *dst.shape, _ct.addressof(arr), int(order), float(cval), _stream())
     return dst
+
+
+# ------------------------------------------------------------------ segmentation inference (seg_ops.hip)
+SEG_LDS_C = 240   # AM_SEG_LDS_C
+
+
+def mirror_axes_mask(axes) -> int:
+    """allowed mirroring axes (spatial, 0..2) -> the kernels' bitmask; its M = 2^len mirrors: bit j of m flips the j-th axis (ascending)."""
+    m = 0
+    for a in axes:
+        if not 0 <= int(a) <= 2:
+            raise ValueError(f"mirroring axis {a} is not a spatial axis of a 3-D volume")
+        m |= 1 << int(a)
+    return m
+
+
+def seg_gather(vol: torch.Tensor, origin, tile, axes_mask: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """vol fp32 [X,Y,Z]; origin = tile start - pad_below (may be negative: zeros outside the volume) -> [M,T0,T1,T2] fp32."""
+    assert vol.dtype == torch.float32 and vol.dim() == 3 and vol.is_contiguous()
+    M = 1 << bin(axes_mask).count("1")
+    if out is None:
+        out = torch.empty(M, *tile, device=vol.device, dtype=torch.float32)
+    assert tuple(out.shape) == (M, *tile) and out.dtype == torch.float32 and out.is_contiguous()
+    hip.lib().seg_gather(vol.data_ptr(), *vol.shape, *(int(o) for o in origin), *(int(t) for t in tile), int(axes_mask), out.data_ptr(), _stream())
+    return out
+
+
+def seg_upcat(u: torch.Tensor, skip: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """cat(nearest_up(u), skip) along channels: u [B,d,h,w,C], skip [B,D,H,W,C] (D = d or 2d) -> [B,D,H,W,2C]."""
+    B, D, H, W, Cc = skip.shape
+    f = D // u.shape[1]
+    assert u.dtype == skip.dtype and u.shape[0] == B and u.shape[-1] == Cc and tuple(v * f for v in u.shape[1:4]) == (D, H, W)
+    if out is None:
+        out = torch.empty(B, D, H, W, 2 * Cc, device=skip.device, dtype=skip.dtype)
+    hip.lib().seg_upcat(_dt(skip), u.data_ptr(), skip.data_ptr(), out.data_ptr(), B, D, H, W, Cc, f, _stream())
+    return out
+
+
+def seg_head(f: torch.Tensor, w: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """plain 1x1 head: f [B,D,H,W,C] -> logits fp32 [B,K,D,H,W]; w fp32 (K,C[,1,1,1]), b fp32 [K]."""
+    B, D, H, W, Cc = f.shape
+    K = w.shape[0]
+    assert w.dtype == torch.float32 and w.numel() == K * Cc and w.is_contiguous() and b.numel() == K
+    out = torch.empty(B, K, D, H, W, device=f.device, dtype=torch.float32)
+    hip.lib().seg_head(_dt(f), f.data_ptr(), B, D, H, W, Cc, w.data_ptr(), b.data_ptr(), K, out.data_ptr(), _stream())
+    return out
+
+
+def seg_head_accumulate(f: torch.Tensor, axes_mask: int, w: torch.Tensor, b: torch.Tensor, gauss: Optional[torch.Tensor], acc: torch.Tensor,
+                        wsum: torch.Tensor, start):
+    """f = the M mirrored predictions of one tile [M,T0,T1,T2,C]; acc fp32 [K,X,Y,Z] and wsum fp32 [X,Y,Z] (padded volume) += the
+    un-flipped mirror mean of the head, Gaussian-weighted, at the tile start."""
+    M, T0, T1, T2, Cc = f.shape
+    K = w.shape[0]
+    assert M == 1 << bin(axes_mask).count("1") and w.dtype == torch.float32 and w.numel() == K * Cc and w.is_contiguous() and b.numel() == K
+    assert acc.dtype == torch.float32 and wsum.dtype == torch.float32 and acc.shape[0] == K and tuple(acc.shape[1:]) == tuple(wsum.shape)
+    assert gauss is None or (gauss.dtype == torch.float32 and gauss.numel() == T0 * T1 * T2)
+    hip.lib().seg_head_accumulate(_dt(f), f.data_ptr(), int(axes_mask), T0, T1, T2, Cc, w.data_ptr(), b.data_ptr(), K, _p(gauss), acc.data_ptr(),
+                                  wsum.data_ptr(), *wsum.shape, *(int(s) for s in start), _stream())
+
+
+def seg_finalize(acc: torch.Tensor, wsum: torch.Tensor, crop_start, crop_size, want_logits: bool = True, want_labels: bool = False):
+    """(logits fp32 [K,X,Y,Z] or None, labels [X,Y,Z] or None): acc / wsum over the crop; labels = argmax (uint8 for K <= 255, else int16)."""
+    K = acc.shape[0]
+    logits = torch.empty(K, *crop_size, device=acc.device, dtype=torch.float32) if want_logits else None
+    labels = torch.empty(*crop_size, device=acc.device, dtype=torch.uint8 if K <= 255 else torch.int16) if want_labels else None
+    hip.lib().seg_finalize(acc.data_ptr(), wsum.data_ptr(), K, *acc.shape[1:], *(int(c) for c in crop_start), *(int(s) for s in crop_size),
+                           _p(logits), _p(labels), labels.element_size() if labels is not None else 1, _stream())
+    return logits, labels

@@ -377,6 +377,34 @@ int am_masked_mean_fwd(int dtype, const void* x, float* mean, int B, int D, int 
 int am_masked_mean_bwd(int dtype, const float* dmean, const float* count, void* dx, int B, int D, int H, int W, int C, const uint8_t* mask,
                        int bshift, const int32_t* active_list, int n_active, void* stream);
 
+/* ---- STUNet segmentation inference (seg_ops.hip): the kernels of nnU-Net's sliding-window predictor around the network
+ * (nnunetv2/inference/predict_from_raw_data.py:622-754, network P/STUNet.py:10-129).  A mirror set is a bitmask `axes` of the spatial axes
+ * (bit a = axis a of [X][Y][Z]); its M = 2^popcount(axes) mirrors are numbered so that bit j of m flips the j-th allowed axis (ascending).
+ *
+ * am_seg_gather: out fp32 [M][T0][T1][T2], out[m][t] = vol[o + flip_m(t)] with vol fp32 [X][Y][Z] (nnU-Net's data[0]) and zero outside it:
+ * o = tile start - pad_below, so pad_nd_image(..., 'constant', value 0) (:665-667) is never materialised; the torch.flip of every mirror
+ * (:605-621) is folded into the read. */
+int am_seg_gather(const float* vol, int X, int Y, int Z, int o0, int o1, int o2, int T0, int T1, int T2, int axes, float* out, void* stream);
+/* Upsample_Layer_nearest + torch.cat((x, skip), 1) (P/STUNet.py:81-83,119-128) with the 1x1 conv moved to the coarse grid (conv and
+ * nearest upsampling commute): y [B][D][H][W][2C] = (u[B][D/f][H/f][W/f][C] upsampled by f in {1, 2} | skip [B][D][H][W][C]).  C % 8 == 0,
+ * 16-byte aligned pointers. */
+int am_seg_upcat(int dtype, const void* u, const void* skip, void* y, int B, int D, int H, int W, int C, int factor, void* stream);
+/* Segmentation head, 1x1 conv C -> K (P/STUNet.py:85 seg_outputs[u]).  w fp32 [K][C] (torch (K, C, 1, 1, 1)), bias fp32 [K].
+ * am_seg_head: f [B][D][H][W][C] -> logits fp32 [B][K][D][H][W] (class-major, what the network returns), any C.
+ * am_seg_head_accumulate: f = the M mirrored predictions of ONE tile [M][T0][T1][T2][C] (C <= AM_SEG_LDS_C); the head is linear, so
+ * sum_m unflip_m(head(f_m)) / M = (W sum_m unflip_m(f_m) + M b) / M is evaluated once on the fp32 sum and
+ *   acc [K][X][Y][Z] (tile at s) += that * gauss[t] (gauss fp32 [T0][T1][T2], NULL: 1),  wsum [X][Y][Z] += gauss[t]
+ * (:728-731; the caller zeroes both; tiles accumulate in order on one stream without atomics: bitwise reproducible). */
+#define AM_SEG_LDS_C 240
+int am_seg_head(int dtype, const void* f, int B, int D, int H, int W, int C, const float* w, const float* bias, int K, float* logits,
+                void* stream);
+int am_seg_head_accumulate(int dtype, const void* f, int axes, int T0, int T1, int T2, int C, const float* w, const float* bias, int K,
+                           const float* gauss, float* acc, float* wsum, int X, int Y, int Z, int s0, int s1, int s2, void* stream);
+/* logits = acc / wsum over the un-padded crop [c, c + (X, Y, Z)) of the padded [Xp][Yp][Zp] (:733-735): logits fp32 [K][X][Y][Z] (NULL: not
+ * written) and / or labels [X][Y][Z] = argmax over k (the lowest index on ties, as torch.argmax; label_bytes 1: uint8, K <= 255; 2: int16). */
+int am_seg_finalize(const float* acc, const float* wsum, int K, int Xp, int Yp, int Zp, int c0, int c1, int c2, int X, int Y, int Z,
+                    float* logits, void* labels, int label_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
