@@ -694,6 +694,11 @@ extern "C" int am_conv3d_partials_rows(int mode, int dtype, int ksize, int strid
   return 0;
 }
 
+extern "C" int am_conv3d_uses_k3(int mode, int dtype, int ksize, int stride, int B, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout,
+                                 int has_masks, int accumulate, int fused_epilogue, int want_partials) {
+  return conv_k3_which(mode, dtype, ksize, stride, B, Di, Hi, Wi, Do, Ho, Wo, Cin, Cout, has_masks, accumulate, fused_epilogue, want_partials);
+}
+
 static int conv3d_impl(int mode, int dtype, int ksize, int stride, const void* x, const void* w_packed,
                        const float* bias, void* y, int B, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo,
                        int Cout, const uint8_t* in_mask, int in_bshift, const uint8_t* out_mask, int out_bshift,

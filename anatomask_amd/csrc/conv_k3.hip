@@ -578,14 +578,47 @@ int conv_k3_rows(int mode, int dtype, int ksize, int stride, int B, int D, int H
   return G * 8;
 }
 
+// Every condition under which conv_k3_launch / conv_k3t_launch take a launch, as ONE predicate each: the launchers decide by them, and
+// conv_k3_which (am_conv3d_uses_k3) answers with them, so a test that asks which kernel serves a launch gets the launcher's own decision.
+static bool k3_serves(int mode, int dtype, int ksize, int stride, int B, int Di, int Hi, int Wi, int Do, int Ho, int Wo, int Cin, int Cout,
+                      bool masks, bool accumulate, bool nbred, bool ep, bool partials) {
+  if (!k3_qualifies(mode, dtype, ksize, stride, B, Di, Hi, Wi, Cin, Cout, masks)) return false;
+  if (accumulate || nbred) return false;
+  if (Di != Do || Hi != Ho || Wi != Wo) return false;
+  if ((size_t)(KED + 1) * Hi * Wi * Cin * 2 >= 0x7fffff00ull) return false;     // the brick's planes must stay below 2 GB (32-bit offsets)
+  int units;
+  (void)k3_grid(B, Di, Hi, Wi, Cout, &units);
+  if (units < K3_MIN_UNITS) return false;
+  if (ep && partials) return false;                // (no caller fuses a store epilogue AND asks for statistics: conv_igemm.hip serves it)
+  return true;
+}
+
+static bool k3t_serves(int mode, int dtype, int ksize, int stride, int B, int Di, int Hi, int Wi, int Do, int Ho, int Wo, int Cin, int Cout,
+                       bool masks, bool accumulate, bool nbred, bool ep, bool partials) {
+  if (mode != AM_CONVT_FWD || dtype != AM_DT_BF16 || ksize != 4 || stride != 2 || masks) return false;
+  if (accumulate || nbred || partials || ep) return false;
+  if (Cin % 32 || Cin < 64 || Cout % 64 || Di % KBD || Hi % KBH || Wi % KBW) return false;      // (>= 2 slabs: the deferred stores of a class ride in the next one's first item)
+  if (Do != 2 * Di || Ho != 2 * Hi || Wo != 2 * Wi) return false;
+  if (B > 255 || Di / KBD > 255 || Hi / KBH > 255 || Wi / KBW > 255) return false;
+  if ((size_t)(KED + 1) * Hi * Wi * Cin * 2 >= 0x7fffff00ull || (size_t)16 * Wo * Cout * 2 >= 0x7fffff00ull) return false;
+  int units;
+  (void)k3_grid(B, Di, Hi, Wi, Cout, &units);          // units = bricks x channel tiles (the eight classes live inside a unit)
+  return units >= K3_MIN_UNITS;
+}
+
+// 0: neither, 1: conv_k3_kernel, 2: its transposed instantiation -- for an am_conv3d launch (no fused input norm, no norm-backward reduce)
+int conv_k3_which(int mode, int dtype, int ksize, int stride, int B, int Di, int Hi, int Wi, int Do, int Ho, int Wo, int Cin, int Cout,
+                  int masks, int accumulate, int ep, int partials) {
+  if (k3t_serves(mode, dtype, ksize, stride, B, Di, Hi, Wi, Do, Ho, Wo, Cin, Cout, masks != 0, accumulate != 0, false, ep != 0, partials != 0)) return 2;
+  if (k3_serves(mode, dtype, ksize, stride, B, Di, Hi, Wi, Do, Ho, Wo, Cin, Cout, masks != 0, accumulate != 0, false, ep != 0, partials != 0)) return 1;
+  return 0;
+}
+
 int conv_k3_launch(int mode, int dtype, int ksize, int stride, ConvArgs& c, void* stream) {
-  if (!k3_qualifies(mode, dtype, ksize, stride, c.B, c.Di, c.Hi, c.Wi, c.Cin, c.Cout, c.in_mask.m || c.out_mask.m)) return 0;
-  if (c.accumulate || c.nb_x) return 0;
-  if (c.Di != c.Do || c.Hi != c.Ho || c.Wi != c.Wo) return 0;
-  if ((size_t)(KED + 1) * c.Hi * c.Wi * c.Cin * 2 >= 0x7fffff00ull) return 0;     // the brick's planes must stay below 2 GB (32-bit offsets)
+  if (!k3_serves(mode, dtype, ksize, stride, c.B, c.Di, c.Hi, c.Wi, c.Do, c.Ho, c.Wo, c.Cin, c.Cout, c.in_mask.m || c.out_mask.m, c.accumulate != 0,
+                 c.nb_x != nullptr, c.ep_scale || c.ep_res || c.ep_act != AM_ACT_NONE, c.partials != nullptr)) return 0;
   int units;
   const int G = k3_grid(c.B, c.Di, c.Hi, c.Wi, c.Cout, &units);
-  if (units < K3_MIN_UNITS) return 0;
 #ifdef AM_ABLATE
   if (getenv("AM_CV_NOK3")) return 0;
   { const char* e_ = getenv("AM_K3_NO32"); if (e_ && atoi(e_) && c.Cout % 64) return 0; }
@@ -602,7 +635,6 @@ int conv_k3_launch(int mode, int dtype, int ksize, int stride, ConvArgs& c, void
   { const char* e = getenv("AM_K3_DBG"); a.dbg = e ? atoi(e) : 0; }
 #endif
   const bool ep = a.ep_scale || a.ep_res || a.ep_act != AM_ACT_NONE;
-  if (ep && a.partials) return 0;                  // (no caller fuses a store epilogue AND asks for statistics: conv_igemm.hip serves it)
   auto kern = ep ? conv_k3_kernel<4, true, false> : (a.partials ? conv_k3_kernel<4, false, true> : conv_k3_kernel<4, false, false>);
   if (c.Cout % 64) kern = ep ? conv_k3_kernel<2, true, false> : (a.partials ? conv_k3_kernel<2, false, true> : conv_k3_kernel<2, false, false>);
   else if (a.partials && !ep && c.stats_sum_only) kern = conv_k3_kernel<4, false, true, false, true>;      // (the rows' sum-of-squares column stays zero)
@@ -624,15 +656,10 @@ int conv_k3_launch(int mode, int dtype, int ksize, int stride, ConvArgs& c, void
 
 // ConvTranspose3d k4 s2 p1 (bf16, dense): 1 = served by the persistent kernel's transposed instantiation, 0 = does not qualify
 int conv_k3t_launch(int mode, int dtype, int ksize, int stride, ConvArgs& c, void* stream) {
-  if (mode != AM_CONVT_FWD || dtype != AM_DT_BF16 || ksize != 4 || stride != 2 || c.in_mask.m || c.out_mask.m) return 0;
-  if (c.accumulate || c.nb_x || c.partials || c.ep_scale || c.ep_res || c.ep_act != AM_ACT_NONE) return 0;
-  if (c.Cin % 32 || c.Cin < 64 || c.Cout % 64 || c.Di % KBD || c.Hi % KBH || c.Wi % KBW) return 0;      // (>= 2 slabs: the deferred stores of a class ride in the next one's first item)
-  if (c.Do != 2 * c.Di || c.Ho != 2 * c.Hi || c.Wo != 2 * c.Wi) return 0;
-  if (c.B > 255 || c.Di / KBD > 255 || c.Hi / KBH > 255 || c.Wi / KBW > 255) return 0;
-  if ((size_t)(KED + 1) * c.Hi * c.Wi * c.Cin * 2 >= 0x7fffff00ull || (size_t)16 * c.Wo * c.Cout * 2 >= 0x7fffff00ull) return 0;
+  if (!k3t_serves(mode, dtype, ksize, stride, c.B, c.Di, c.Hi, c.Wi, c.Do, c.Ho, c.Wo, c.Cin, c.Cout, c.in_mask.m || c.out_mask.m, c.accumulate != 0,
+                  c.nb_x != nullptr, c.ep_scale || c.ep_res || c.ep_act != AM_ACT_NONE, c.partials != nullptr)) return 0;
   int units;
   const int G = k3_grid(c.B, c.Di, c.Hi, c.Wi, c.Cout, &units);          // units = bricks x channel tiles (the eight classes live inside a unit)
-  if (units < K3_MIN_UNITS) return 0;
 #ifdef AM_ABLATE
   { const char* e_ = getenv("AM_CV_NOK3T"); if (e_ && atoi(e_)) return 0; }
 #endif

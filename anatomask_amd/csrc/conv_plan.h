@@ -152,5 +152,9 @@ int conv_gather_rows(int mode, int dtype, int ksize, int stride, int B, int Do, 
 int conv_k3_launch(int mode, int dtype, int ksize, int stride, ConvArgs& a, void* stream);
 int conv_k3_rows(int mode, int dtype, int ksize, int stride, int B, int D, int H, int W, int Cin, int Cout, int masks);
 int conv_k3t_launch(int mode, int dtype, int ksize, int stride, ConvArgs& c, void* stream);   // ConvTranspose3d k4 s2 p1 on the same kernel
+// which of the two serves an am_conv3d launch of this shape and these options (0 neither, 1 conv_k3_kernel, 2 its transposed instantiation):
+// the launchers' own predicates
+int conv_k3_which(int mode, int dtype, int ksize, int stride, int B, int Di, int Hi, int Wi, int Do, int Ho, int Wo, int Cin, int Cout,
+                  int masks, int accumulate, int ep, int partials);
 
 }  // namespace amconv

@@ -2032,9 +2032,9 @@ int am_stem_conv_fwd(int dtype, const float* x, int B, int D, int H, int W, int 
   CHK_C_NARROW(C);
   if (ksize != 1 && ksize != 3) return -2;
   Geo g = mkgeo(dtype, false, B, D, H, W, C, mask, bshift, fd, fh, fw);
-  const bool geo_bad = mask && !geo_ok(B, D, H, W);          // only the LINEAR kernels decode voxel indices by reciprocal multiply
   hipStream_t st = (hipStream_t)stream;
   if (!mask || bshift != 4 || D % 16 || H % 16 || W % 16) return -2;      // stage-0 tensor: 16^3 patches
+  if ((long)B * (D / SBD) * (H / SBH) * (W / SBW) > 0x7fffffffL) return -4;      // (the brick count, and with it the partials row count, is an int)
   if (partial_rows_written) *partial_rows_written = B * (D / SBD) * (H / SBH) * (W / SBW);
   if (dtype == AM_DT_BF16 && ksize == 3 && active_list && n_active > 0 && (C == 32 || C == 64 || C == 96) && B <= 255 && fd <= 255 && fh <= 255 && fw <= 255) {
     const MaskView mv{mask, fd, fh, fw, bshift};
@@ -2045,7 +2045,8 @@ int am_stem_conv_fwd(int dtype, const float* x, int B, int D, int H, int W, int 
     if (partial_rows_written) *partial_rows_written = n_active;
     return 0;
   }
-  if (geo_bad) return -4;
+  // (the brick kernel below takes (b, d, h, w) from its brick index and the mask by coordinates: no reciprocal-multiply voxel decode, so
+  // the linear kernels' geometry limit does not apply -- fp32 storage at batch 16 of 128^3 runs here)
   const int nb = B * (D / SBD) * (H / SBH) * (W / SBW);
   const int pad_ = ksize / 2;
   size_t fl = (size_t)C * ksize * ksize * ksize;
@@ -2068,7 +2069,6 @@ int am_stem_conv_wgrad(int dtype, const float* x, const void* dy, int B, int D, 
   CHK_C_NARROW(C);
   if (ksize != 1 && ksize != 3) return -2;
   Geo g = mkgeo(dtype, true, B, D, H, W, C, mask, bshift, fd, fh, fw);
-  const bool geo_bad = mask && !geo_ok(B, D, H, W);          // only the LINEAR kernels decode voxel indices by reciprocal multiply
   hipStream_t st = (hipStream_t)stream;
   if (!mask || bshift != 4 || D % 16 || H % 16 || W % 16) return -2;
   if (dtype == AM_DT_BF16 && active_list && n_active > 0 && (C == 32 || C == 64 || C == 96) && B <= 255 && fd <= 255 && fh <= 255 && fw <= 255) {
@@ -2097,7 +2097,8 @@ int am_stem_conv_wgrad(int dtype, const float* x, const void* dy, int B, int D, 
     }
     return 0;
   }
-  if (geo_bad) return -4;
+  // (a brick walk by coordinates, as am_stem_conv_fwd's: the linear kernels' geometry limit does not apply)
+  if ((long)B * (D / SBD) * (H / SBH) * (W / SBW) > 0x7fffffffL) return -4;
   int nb = B * (D / SBD) * (H / SBH) * (W / SBW);
   if (nb > 1024) nb = 1024;                                   // persistent workgroups: one atomic flush each
   const int pad_ = ksize / 2;

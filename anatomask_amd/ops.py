@@ -99,7 +99,10 @@ def packed_dims(dtype: torch.dtype, rows: int, k: int):
 
 
 class ConvPartials:
-    """Per-workgroup per-channel (sum, sumsq) rows a conv launch leaves behind for the norm / bias-grad that follows."""
+    """Per-workgroup per-channel (sum, sumsq) rows a conv launch leaves behind for the norm / bias-grad that follows.
+    sum_only: the launch was asked for the SUM column alone (conv3d(partials_sum_only=True)); the sum-of-squares column may hold zeros,
+    so everything that reads it (statistics, norm-backward sums) refuses such rows."""
+    sum_only = False
 
     def __init__(self, mode, ksize, stride, B, out_spatial, cout, device, out_sparse=False, out_bshift=0, dtype=hip.DT_F32, cin=64, n_active=0):
         import ctypes
@@ -109,12 +112,14 @@ class ConvPartials:
         self.t = torch.empty(self.rows, cout, 2, device=device, dtype=torch.float32)
 
     def reduce(self, sums: Optional[torch.Tensor] = None, sum_accum: Optional[torch.Tensor] = None):
+        assert sums is None or not self.sum_only, "sum-only rows carry no sum of squares"
         hip.lib().partials_reduce(self.t.data_ptr(), self.rows, self.C, _p(sums), _p(sum_accum), _stream())
 
     def finalize(self, st: Optional["NormStats"], gamma=None, beta=None, eps: float = 0.0, run_mean=None, run_var=None,
                  momentum: float = 0.1, num_batches_tracked=None, sum_accum: Optional[torch.Tensor] = None):
         """partials -> per-channel sums -> mean / rstd / scale / shift of `st` (+ BN running stats, num_batches_tracked) in ONE
         launch (am_partials_finalize); st None: only `sum_accum[c] += sum` (bias gradients)."""
+        assert st is None or not self.sum_only, "sum-only rows carry no sum of squares"
         ws = _stats_workspace(self.t.device, self.C)
         if st is None:
             hip.lib().partials_finalize(self.t.data_ptr(), self.rows, self.C, ws.data_ptr(), None, 1.0, None, None, 0.0, None, None, None,
@@ -128,6 +133,7 @@ class ConvPartials:
 
     def finalize_bwd(self, st: "NormStats", gamma: torch.Tensor, sc: "NormBwdScratch", dgamma=None, dbeta=None, dbeta2=None):
         """rows of a conv3d(norm_bwd=...) launch -> k0 / k1 / k2 of the apply pass + the affine gradients (am_norm_bwd_from_partials)."""
+        assert not self.sum_only, "sum-only rows carry no second column"
         ws = _stats_workspace(self.t.device, self.C)
         hip.lib().norm_bwd_from_partials(self.t.data_ptr(), self.rows, self.C, ws.data_ptr(), _p(st.count_ptr), float(st.count_host),
                                          gamma.data_ptr(), st.mean.data_ptr(), st.rstd.data_ptr(), sc.k[0].data_ptr(), sc.k[1].data_ptr(),
@@ -260,6 +266,7 @@ def conv3d(mode: int, x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[to
                      ep_res.data_ptr() if ep_res is not None else None, int(ep_act), alp, aln, _ROWS_ADDR if part else None, _stream())
     if part is not None:
         part.rows = rows.value                                   # what this launch actually wrote (<= the allocated bound)
+        part.sum_only = bool(partials_sum_only)
     return (out, part) if want_partials else out
 
 

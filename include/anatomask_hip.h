@@ -95,6 +95,12 @@ int am_packed_dims(int dtype, int rows, int k, int* rows_padded, int* k_padded);
 int am_conv3d_partials_rows(int mode, int dtype, int ksize, int stride, int B, int Do, int Ho, int Wo, int Cin, int Cout,
                             int out_sparse, int out_bshift /* the launch's out_mask != NULL and its block shift: they select the brick */,
                             int n_active, int* rows /* upper bound: size the partials buffer with it */);
+/* 0 / 1 / 2 (an answer, not an error code): which persistent LDS-DMA kernel of conv_k3.hip serves an am_conv3d launch of this shape and these
+ * options -- 1: conv_k3_kernel (dense bf16 k3 s1 forward / data gradient), 2: its transposed instantiation (dense bf16 ConvTranspose3d k4 s2 p1),
+ * 0: neither (conv_igemm.hip / conv_rw.hip / conv_gather.hip serve it).  Evaluates the predicates the launchers themselves decide by.
+ * has_masks: in_mask or out_mask != NULL; fused_epilogue: ep_scale, ep_res or ep_act given; want_partials: partials != NULL. */
+int am_conv3d_uses_k3(int mode, int dtype, int ksize, int stride, int B, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout,
+                      int has_masks, int accumulate, int fused_epilogue, int want_partials);
 /* partials [rows][C][2] -> sums[C][2] (double, overwritten; may be NULL) and/or sum_accum[C] += sum (may be NULL) */
 int am_partials_reduce(const float* partials, int rows, int C, double* sums, float* sum_accum, void* stream);
 

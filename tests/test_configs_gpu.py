@@ -219,6 +219,7 @@ def test_config2_stunet_b_128_fp32_storage_step_vs_oracle(f32_split):
 # against oracle.train_step.  Every compared step runs the persistent LDS-DMA kernels (conv_k3, its ConvT instantiation, wgrad_k3) that
 # carry 70 % of a step; steps 2 and 3 run them on UPDATED weights with a teacher that is no longer the student.
 NS_N, NS_EPOCH, NS_TOTAL, NS_LR, NS_DECAY = 3, 500, 999, 1e-4, 0.999
+GPU_NSTEP_UPDATE_MEDIAN = 0.28     # fp32 storage, N-step update median vs the oracle: measured 0.094 (exact products), 0.115 (split), 0.099 (recipe shape); 3 x 0.094
 
 
 def _ns_draws(cfg):
@@ -277,7 +278,7 @@ def test_config2_n_steps_vs_oracle(mode):
     """mode "f32-recipe": the same three steps on the reference's SHIPPED recipe shape 112 x 112 x 128 (P/pretrain_AntoMask.py:188,209: 392
     patches, 58 of the 235 masked ones hard; the ragged 28^3 / 14^3 / 7^3 grids take the tail branches of the brick kernels), exact fp32."""
     from anatomask_amd.trainer import AnatoMaskTrainer
-    from tests.test_oracle_golden import NSTEP_UPDATE_MEDIAN, NSTEP_WEIGHT_MAX, NSTEP_WEIGHT_MEDIAN, STEP1_FLIPPED, STEP1_UPDATE_MEDIAN
+    from tests.test_oracle_golden import NSTEP_WEIGHT_MAX, NSTEP_WEIGHT_MEDIAN, STEP1_FLIPPED, STEP1_UPDATE_MEDIAN
     recipe = mode == "f32-recipe"
     cfg, W0, draws, st, outs, snap1 = _oracle_nsteps_b128((112, 112, 128)) if recipe else _oracle_nsteps_b128()
     mode = "f32" if recipe else mode
@@ -356,8 +357,9 @@ def test_config2_n_steps_vs_oracle(mode):
         assert med < 1.3 * imed and mx[2] < 1.5 * imx and wmed < 1.3 * iw and wmx < 1.5 * iwx, (med, imed, mx, imx)
         assert max(r[2] for r in bn) < 5e-2
     else:
-        assert med < NSTEP_UPDATE_MEDIAN and wmed < NSTEP_WEIGHT_MEDIAN and wmx < NSTEP_WEIGHT_MAX, (med, wmed, wmx)
-        assert float(np.median([r[2] for r in rows_e])) < NSTEP_UPDATE_MEDIAN
+        # (tests/test_oracle_golden.py's NSTEP_UPDATE_MEDIAN, 0.45, is the tiny CPU configuration's bound; at full size the median is asserted at <= 3 x what this test measures)
+        assert med < GPU_NSTEP_UPDATE_MEDIAN and wmed < NSTEP_WEIGHT_MEDIAN and wmx < NSTEP_WEIGHT_MAX, (med, wmed, wmx)
+        assert float(np.median([r[2] for r in rows_e])) < GPU_NSTEP_UPDATE_MEDIAN
         for k, n_el, e, c, _ in rows + rows_e:
             if n_el >= 64:
                 assert e < 0.9 and c > 0.5, (k, n_el, e, c)
@@ -526,30 +528,39 @@ def test_config5_stunet_h_192_recompute_properties():
 #   per gradient tensor: the bf16 step is as far from the fp32-storage step as an ideal bf16 evaluation is from fp32 on that model
 #   (medians measured against the oracle at the reduced patches: L 0.47, H 0.60) -- median <= 1.25 x that, no tensor beyond 1.6 x its
 #   worst tensor + 0.05, and every gradient tensor is finite and non-zero where the fp32 one is.
-FULL_MEDIAN = {"L": 0.47, "H": 0.60}        # ideal bf16 emulation vs fp32, median rel-L2 per tensor (profiles/r03_experiments.md)
-FULL_WORST = {"L": 0.75, "H": 0.92}         # ... worst tensor
+# "B": STUNet-B at 128^3 itself, B = 1, against the CPU oracle (what test_config2_stunet_b_128_bf16_step_vs_oracle prints as "ideal bf16
+# emulation vs fp32": rel-L2 median 2.802e-01 max 4.304e-01) -- the bounds of the B = 16 step below
+FULL_MEDIAN = {"L": 0.47, "H": 0.60, "B": 0.28}        # ideal bf16 emulation vs fp32, median rel-L2 per tensor (profiles/r03_experiments.md)
+FULL_WORST = {"L": 0.75, "H": 0.92, "B": 0.43}         # ... worst tensor
 
 
-def _bf16_vs_fp32_storage_full_size(size, patch, mask_ratio, recompute, seed):
+def _bf16_vs_fp32_storage_full_size(size, patch, mask_ratio, recompute, seed, B=1):
+    """B > 1: also the peak device memory of each storage's step (printed) and, on the bf16 model, a second step in the hard-mask regime
+    with the size-independent invariants of _step_properties at that batch."""
     from anatomask_amd import modules as M
     from anatomask_amd.trainer import AnatoMaskTrainer
     kw = M.STUNET_CONFIGS[size]
     cfg = O.Config(kw["dims"], kw["depth"], kw["width"], (patch,) * 3, mask_ratio)
     W0 = O.seeded_state(cfg, seed)
-    x = O.smooth_volume(1, cfg.input_size, seed + 1).to(DEV)
+    x = O.smooth_volume(B, cfg.input_size, seed + 1).to(DEV)
     g = torch.Generator().manual_seed(seed + 2)
-    mask1 = O.random_mask(cfg, 1, g)
-    keys = torch.rand(1, cfg.L, generator=g)
+    mask1 = O.random_mask(cfg, B, g)
+    keys = torch.rand(B, cfg.L, generator=g)
     res = {}
     for dtype, name in ((torch.float32, "fp32"), (torch.bfloat16, "bf16")):
+        torch.cuda.reset_peak_memory_stats()
         m = _build(cfg, W0, dtype=dtype, recompute=recompute)
         tr = AnatoMaskTrainer(m, lr=1e-4, ema_decay=0.999, total_epochs=1000, distributed=False)
         out = tr.step(x, epoch=0, mask1=mask1, keys=keys)
         torch.cuda.synchronize()
         live = [k for k in m._pnames if k not in m._dead]
-        res[name] = {"loss": out["loss"].item(), "gn": out["grad_norm"].item(), "mask": out["mask"].view(1, -1).bool().cpu(),
+        res[name] = {"loss": out["loss"].item(), "gn": out["grad_norm"].item(), "mask": out["mask"].view(B, -1).bool().cpu(),
                      "recon": out["recon_loss"].double().cpu(), "rl": out["rec_loss"].double().cpu(),
                      "grads": {k: m._G[k].detach().double().cpu().reshape(-1) for k in live}}
+        if B > 1:
+            print(f"STUNet-{size} {patch}^3 B={B} {name} storage: peak device memory of the step {torch.cuda.max_memory_allocated() / 2 ** 30:.1f} GiB")
+            if name == "bf16":
+                _step_properties(tr, cfg, tr.step(x, epoch=500), B, 500, 999)
         del m, tr, out
         torch.cuda.empty_cache()
     a, b = res["fp32"], res["bf16"]
@@ -580,6 +591,22 @@ def test_config4_stunet_l_160_mask07_bf16_vs_fp32_storage_full_size():
 
 def test_config5_stunet_h_192_recompute_bf16_vs_fp32_storage_full_size():
     _bf16_vs_fp32_storage_full_size("H", 192, 0.6, True, 141)
+
+
+def test_config2_stunet_b_128_batch16_bf16_vs_fp32_storage():
+    """bench.py's own launch set: ONE AnatoMask step of STUNet-B at 128^3, mask 0.6, B = 16 (level-0 decoder activations of exactly 2^32
+    bytes, sample 8 at byte 2^31) in bf16 storage -- conv_k3 / its transposed instantiation / wgrad_k3 / the row-walk norm kernels --
+    against the HIP fp32-storage step on the same weights, volume, mask and keys.  The fp32-storage step is pinned to the CPU oracle at
+    B = 1 (test_config2_stunet_b_128_fp32_storage_step_vs_oracle) and is served by conv_igemm / conv_wgrad, not by the persistent kernels:
+    an independent addressing path.  Bounds: FULL_MEDIAN / FULL_WORST["B"] with the helper's factors; the fp32 side runs WITHOUT
+    activation recomputation (its peak memory is printed).
+    Measured on MI355X: loss 1.010469 / 1.010464 (rel 5e-6, bound 1e-4), gradient norm 0.21938 / 0.21927 (5e-4, bound 2e-2), teacher l2 4.8e-5 (bound
+    2.4e-2); 82 gradient tensors, median 0.214 (bound 1.25 x 0.28), worst 0.345 (bound 1.6 x 0.43 + 0.05), min cos 0.946; peak device memory of
+    the step 116.5 GiB (fp32 storage) / 59.0 GiB (bf16); 7 s."""
+    total = torch.cuda.get_device_properties(0).total_memory
+    if total < 128 * 2 ** 30:
+        pytest.skip(f"device has {total / 2 ** 30:.0f} GiB in total; the fp32-storage step at B = 16 peaks at 117 GiB")
+    _bf16_vs_fp32_storage_full_size("B", 128, 0.6, False, 151, B=16)
 
 
 def test_config2_bf16_training_tracks_fp32_storage_training():
