@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <initializer_list>
 
 typedef uint16_t bf16_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -162,35 +163,113 @@ struct MaskView {
   }
 };
 
-// Run `f` once per DEVICE of this process (not once per process): kernel attributes (hipFuncSetAttribute) and device properties are
-// per device, and one process may drive several (one process per GPU is the deployment, but nothing here may assume it).
-// Idempotent work only: two threads may both run f for the same device.
-struct PerDeviceOnce {
-  unsigned long long done = 0;
-  template <typename F> __host__ void run(F&& f) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (__atomic_load_n(&done, __ATOMIC_ACQUIRE) & bit) return;
-    f(dev);
-    __atomic_fetch_or(&done, bit, __ATOMIC_RELEASE);
-  }
-};
+// MFMA tile row -> output channel.  D row 4g+r of cout tile i lands in lane group g, register r; rows are assigned so that
+// a lane's registers of tiles (2h, 2h+1) are the 8 CONSECUTIVE channels h*32 + g*8 .. +8: the epilogue stores 16 bytes per
+// lane and the 4 lane groups of a voxel write one contiguous 64-byte run (instead of 8-byte pieces of four 32-byte runs).
+__device__ __forceinline__ int crow(int R) { return ((R >> 5) << 5) + (((R >> 2) & 3) << 3) + (((R >> 4) & 1) << 2) + (R & 3); }
 
+// Ablation switches exist only in the tools build (anatomask_amd.build --ablate -> libanatomask_hip_ablate.so); in the product
+// library AM_DBG() is the constant false and no environment variable is ever read.
+#ifdef AM_ABLATE
+#define AM_DBG(a_, bit_) (((a_).dbg & (bit_)) != 0)
+#else
+#define AM_DBG(a_, bit_) false
+#endif
+
+// ================================================================== host: errors and launches
 #define AM_CHECK_LAUNCH() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
-// launch with a clean error slate: hipGetLastError() is per-thread sticky and torch's own probing calls
-// can leave a benign error behind that would otherwise be mis-attributed to our launch
 // an API call inside an entry point that promises "0 or a hipError_t": its failure is the entry point's return value
 #define AM_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return (int)e_; } while (0)
+// launch with a clean error slate: hipGetLastError() is per-thread sticky and torch's own probing calls
+// can leave a benign error behind that would otherwise be mis-attributed to our launch
 #define AM_LAUNCH(...) do { (void)hipGetLastError(); hipLaunchKernelGGL(__VA_ARGS__); } while (0)
 // The kernel-selection stages (conv_rw / conv_gather / conv_k3 / conv_k3t / conv_wgk3 _launch) answer 1 = served, 0 = the shape does not
 // qualify.  hipErrorInvalidValue IS 1 (what a rejected launch configuration returns), so a failure inside a stage is -(1000 + hipError_t):
 // never mistaken for "served", and distinct from the entry points' small negative argument errors.
 #define AM_STAGE_ERR(e) (-(1000 + (int)(e)))
 #define AM_CHECK_LAUNCH_STAGE() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return AM_STAGE_ERR(e_); } while (0)
-// opt a kernel in to 160 KB of dynamic LDS once per device; a refused opt-in is the stage's (sticky) failure, not a silent fall-through
-#define AM_LDS_OPTIN_STAGE(kern) do { \
-    static PerDeviceOnce once_; static int err_ = 0; \
-    once_.run([&](int) { hipError_t e_ = hipFuncSetAttribute((const void*)(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-                         if (e_ != hipSuccess) err_ = (int)e_; (void)hipGetLastError(); }); \
-    if (err_) return AM_STAGE_ERR(err_); } while (0)
+#define AM_HIP_STAGE(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return AM_STAGE_ERR(e_); } while (0)
+
+// ================================================================== host: per-device state
+// Kernel attributes (hipFuncSetAttribute) and device properties are per DEVICE, not per process: one process per GPU is the deployment,
+// but nothing here may assume it.  am_per_device keeps one nonzero int per device ordinal (& 63) for EACH CALL SITE -- the state belongs
+// to the type of `init`, and every lambda expression (in every instantiation of a template around it) is a type of its own.  The first
+// call on a device runs init(dev) and publishes what it returns; later calls are one atomic load.  Two threads may both run init for the
+// same device, so it does idempotent work only, and they publish the same value.  A caller that needs the ordinal twice asks for it
+// once (am_device) and passes it on: hipGetDevice is the only runtime call a launch pays for all of this.
+inline int am_device() { int dev = 0; (void)hipGetDevice(&dev); return dev; }
+template <typename F> inline int am_per_device(F&& init, int dev = am_device()) {
+  static int slot[64];                            // 0: init has not run for this device
+  int v = __atomic_load_n(&slot[dev & 63], __ATOMIC_ACQUIRE);
+  if (!v) { v = init(dev); __atomic_store_n(&slot[dev & 63], v, __ATOMIC_RELEASE); }
+  return v;
+}
+// compute units of the current device (256 when the runtime does not say)
+inline int am_cu_count(int dev = am_device()) {
+  return am_per_device([](int d) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || n <= 0) n = 256;
+    (void)hipGetLastError();
+    return n;
+  }, dev);
+}
+// Opt the kernels in to all of the CU's 160 KB of LDS as dynamic LDS, once per device and set of kernels:
+// 160 KB less what the kernel declares statically -- the runtime refuses a cap that cannot fit beside the static part (256 bytes in
+// conv_igemm / conv_wgrad / dwconv kernels).  The answer is that device's own and stays what it was: a refused opt-in is the caller's
+// failure -- AM_HIP() in an entry point, AM_HIP_STAGE() in a stage -- on that device only, never a silent fall-through.
+template <auto... Kerns> inline hipError_t am_lds_optin(int dev = am_device()) {
+  return (hipError_t)(am_per_device([](int) {
+    hipError_t e = hipSuccess;
+    for (const void* k : {(const void*)Kerns...}) {
+      hipFuncAttributes fa;
+      hipError_t r = hipFuncGetAttributes(&fa, k);
+      if (r == hipSuccess) r = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - (int)fa.sharedSizeBytes);
+      if (e == hipSuccess) e = r;
+    }
+    (void)hipGetLastError();
+    return 1 + (int)e;
+  }, dev) - 1);
+}
+
+// ================================================================== host: runtime value -> compile-time choice
+// Each helper turns one runtime argument of an entry point into a tag and hands it to a generic lambda; the entry point writes its
+// launch ONCE, inside that lambda, with the tags as template arguments (`typename decltype(t)::type`, and an am_int converts to its
+// value in a constant expression).  Which instantiations exist is what these helpers can produce, nothing else.
+template <typename T> struct am_type { using type = T; };
+template <int V> struct am_int { static constexpr int value = V; constexpr operator int() const { return V; } };
+// storage dtype -> float / bf16_t
+template <typename F> inline void am_by_dtype(int dtype, F&& f) { if (dtype == AM_DT_BF16) f(am_type<bf16_t>{}); else f(am_type<float>{}); }
+// v is one of Vs... -> f(am_int<v>), true; else false and f does not run
+template <int... Vs, typename F> inline bool am_by_int(int v, F&& f) { return ((v == Vs ? (f(am_int<Vs>{}), true) : false) || ...); }
+// ... both at once: f(type, am_int<v>)
+template <int... Vs, typename F> inline bool am_by_dtype_int(int dtype, int v, F&& f) {
+  return am_by_int<Vs...>(v, [&](auto k) { am_by_dtype(dtype, [&](auto t) { f(t, k); }); });
+}
+// activation code x "the derivative comes from the saved output" -> the (ACT_, OUT_) pair of a specialised norm kernel; any other
+// code takes the generic instantiation (-1, 0), which reads both at run time.  (Codes: AM_ACT_NONE 0, AM_ACT_LRELU 1, AM_ACT_RELU6 2.)
+template <typename F> inline void am_by_act(int act, bool has_out, F&& f) {
+  if (act == 0) f(am_int<0>{}, am_int<0>{});
+  else if (act == 1 && has_out) f(am_int<1>{}, am_int<1>{});
+  else if (act == 1) f(am_int<1>{}, am_int<0>{});
+  else if (act == 2 && has_out) f(am_int<2>{}, am_int<1>{});
+  else if (act == 2) f(am_int<2>{}, am_int<0>{});
+  else f(am_int<-1>{}, am_int<0>{});
+}
+// Linear (Walk) kernels, f(type, threads): 256 threads, or 512 for an fp32 row of more than 256 16-byte chunks (C > 1024)
+template <typename F> inline void am_by_walk(int dtype, int C, F&& f) {
+  if (dtype == AM_DT_BF16) f(am_type<bf16_t>{}, am_int<256>{});
+  else if (C / 4 > 256) f(am_type<float>{}, am_int<512>{});
+  else f(am_type<float>{}, am_int<256>{});
+}
+// ... and those of them with a specialised activation, f(type, threads, ACT_, OUT_): the 512-thread fp32 kernels exist in the generic
+// form (-1, 0) only
+template <typename F> inline void am_by_walk_act(int dtype, int C, int act, bool has_out, F&& f) {
+  am_by_walk(dtype, C, [&](auto t, auto nt) {
+    if constexpr (nt == 512) f(t, nt, am_int<-1>{}, am_int<0>{});
+    else am_by_act(act, has_out, [&](auto a, auto o) { f(t, nt, a, o); });
+  });
+}
+// a voxel row is 16-byte chunks on the threads of ONE workgroup: C % 8 == 0, C <= 2048, and fp32 rows (4 channels per chunk) at most
+// f32_max channels -- 2048 where the entry point has 512-thread instantiations, 1024 where it launches 256 threads.  Refuse, never
+// mis-compute: with too few threads such a row leaves every thread idle and the output untouched.
+inline bool am_row_ok(int dtype, int C, int f32_max) { return C > 0 && C % 8 == 0 && C <= 2048 && (dtype == AM_DT_BF16 || C <= f32_max); }

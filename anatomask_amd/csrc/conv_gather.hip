@@ -315,9 +315,9 @@ bool ga_geometry(GaGeo& G, int mode, int dtype, int k, int stride, int B, int Do
 
 template <int NS, int KSL>
 int ga_launch(ConvArgs& a, GaArgs& r, hipStream_t st) {
-  auto kern = conv_gather_kernel<NS, 2, KSL>;
+  constexpr auto kern = conv_gather_kernel<NS, 2, KSL>;
   constexpr size_t lds = (size_t)2 * 16 * NS * (KSL * 64 + 16);
-  AM_LDS_OPTIN_STAGE(kern);
+  AM_HIP_STAGE(am_lds_optin<kern>());
   r.nkg = a.Cin / (32 * KSL);
   dim3 grid((unsigned)(((r.ntile + 7) / 8) * 8 * r.ny * r.ncls), 1, 1);
   AM_LAUNCH(kern, grid, dim3(256), lds, st, a, r);

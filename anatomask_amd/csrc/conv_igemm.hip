@@ -567,10 +567,9 @@ __global__ __launch_bounds__(256, (TGS == 2 && BD * BH * BW <= 256) ? 3 : 2) voi
 template <typename T, int BD, int BH, int BW, int NS, int NIT, int TGS = 3, bool HR = false, bool NB = false, bool HT = false>
 int launch(Plan& P, hipStream_t st) {
   ConvArgs& a = P.a;
-  auto kern = conv_igemm_kernel<T, BD, BH, BW, NS, NIT, TGS, HR, NB, HT>;
-  static PerDeviceOnce lds_cap;                   // per instantiation and device: lift the 48 KB dynamic-LDS default to the CU's 160 KB
-  lds_cap.run([&](int) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); (void)hipGetLastError(); });
+  constexpr auto kern = conv_igemm_kernel<T, BD, BH, BW, NS, NIT, TGS, HR, NB, HT>;
   if (P.lds > 160 * 1024) return -3;
+  AM_HIP(am_lds_optin<kern>());
   const unsigned nbrick = a.plist ? (unsigned)a.nlive : (unsigned)(a.B * a.nbd * a.nbh * a.nbw);
   a.ny = (a.Cout + 16 * NS - 1) / (16 * NS);
   const unsigned nsib = (unsigned)(a.ny * a.nclass);
@@ -735,12 +734,9 @@ static int conv3d_impl(int mode, int dtype, int ksize, int stride, const void* x
       if (rt == 1) return 0;
     }
     if (!in_scale) {                               // dense k3 s1 at decoder sizes: the persistent LDS-DMA kernel (conv_k3.hip)
-      const int rk = conv_k3_launch(mode, dtype, ksize, stride, a, stream);
+      const int rk = conv_k3_launch(mode, dtype, ksize, stride, a, stream, partial_rows_written);
       if (rk < 0) return rk;
-      if (rk == 1) {
-        if (partial_rows_written) *partial_rows_written = conv_k3_rows(mode, dtype, ksize, stride, B, Do, Ho, Wo, Cin, Cout, 0);
-        return 0;
-      }
+      if (rk == 1) return 0;
     }
     const int rc = nb_x ? 0 : conv_rw_launch(mode, dtype, ksize, stride, a, active_list, n_active, stream);   // (the fused reduce lives in conv_igemm_kernel only)
     if (rc < 0) return rc;

@@ -549,16 +549,14 @@ __global__ __launch_bounds__(512, 2) void conv_k3_kernel(K3Args a) {
 
 namespace amconv {
 
-// rows of partial sums a launch of this kernel writes (8 per workgroup), or 0 when the shape does not qualify
-static int k3_grid(int B, int D, int H, int W, int Cout, int* units) {
-  const int nb = B * (D / KBD) * (H / KBH) * (W / KBW), ny = Cout % 64 ? Cout / 32 : Cout / 64;      // (32-channel tiles for Cout = 32, 96, 160)
-  *units = nb * ny;
-  int cus = 256;
-  static int cached = 0;
-  if (!cached) { hipDeviceProp_t p; int dev = 0; (void)hipGetDevice(&dev); if (hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) cached = p.multiProcessorCount; else cached = 256; (void)hipGetLastError(); }
-  cus = cached;
+// units of a launch = bricks x channel tiles (32-channel tiles for Cout = 32, 96, 160; the transposed kernel's eight classes live inside a unit)
+static int k3_tiles(int Cout) { return Cout % 64 ? Cout / 32 : Cout / 64; }
+static int k3_units(int B, int D, int H, int W, int Cout) { return B * (D / KBD) * (H / KBH) * (W / KBW) * k3_tiles(Cout); }
+// ... and its workgroups on the device `dev`: one per CU at most
+static int k3_grid(int units, int Cout, int dev = am_device()) {
+  const int cus = am_cu_count(dev), ny = k3_tiles(Cout);
   // a multiple of the channel-tile count: a workgroup's units (u, u + G, ...) then all have the same channel tile
-  const int G = *units < cus ? *units : cus;
+  const int G = units < cus ? units : cus;
   return G - G % ny > 0 ? G - G % ny : ny;
 }
 
@@ -570,12 +568,12 @@ static bool k3_qualifies(int mode, int dtype, int ksize, int stride, int B, int 
   return true;
 }
 
+// rows of partial sums a launch of this kernel writes on the current device (8 per workgroup), or 0 when the shape does not qualify
 int conv_k3_rows(int mode, int dtype, int ksize, int stride, int B, int D, int H, int W, int Cin, int Cout, int masks) {
   if (!k3_qualifies(mode, dtype, ksize, stride, B, D, H, W, Cin, Cout, masks != 0)) return 0;
-  int units;
-  const int G = k3_grid(B, D, H, W, Cout, &units);
+  const int units = k3_units(B, D, H, W, Cout);
   if (units < K3_MIN_UNITS) return 0;
-  return G * 8;
+  return k3_grid(units, Cout) * 8;
 }
 
 // Every condition under which conv_k3_launch / conv_k3t_launch take a launch, as ONE predicate each: the launchers decide by them, and
@@ -586,9 +584,7 @@ static bool k3_serves(int mode, int dtype, int ksize, int stride, int B, int Di,
   if (accumulate || nbred) return false;
   if (Di != Do || Hi != Ho || Wi != Wo) return false;
   if ((size_t)(KED + 1) * Hi * Wi * Cin * 2 >= 0x7fffff00ull) return false;     // the brick's planes must stay below 2 GB (32-bit offsets)
-  int units;
-  (void)k3_grid(B, Di, Hi, Wi, Cout, &units);
-  if (units < K3_MIN_UNITS) return false;
+  if (k3_units(B, Di, Hi, Wi, Cout) < K3_MIN_UNITS) return false;
   if (ep && partials) return false;                // (no caller fuses a store epilogue AND asks for statistics: conv_igemm.hip serves it)
   return true;
 }
@@ -601,9 +597,7 @@ static bool k3t_serves(int mode, int dtype, int ksize, int stride, int B, int Di
   if (Do != 2 * Di || Ho != 2 * Hi || Wo != 2 * Wi) return false;
   if (B > 255 || Di / KBD > 255 || Hi / KBH > 255 || Wi / KBW > 255) return false;
   if ((size_t)(KED + 1) * Hi * Wi * Cin * 2 >= 0x7fffff00ull || (size_t)16 * Wo * Cout * 2 >= 0x7fffff00ull) return false;
-  int units;
-  (void)k3_grid(B, Di, Hi, Wi, Cout, &units);          // units = bricks x channel tiles (the eight classes live inside a unit)
-  return units >= K3_MIN_UNITS;
+  return k3_units(B, Di, Hi, Wi, Cout) >= K3_MIN_UNITS;
 }
 
 // 0: neither, 1: conv_k3_kernel, 2: its transposed instantiation -- for an am_conv3d launch (no fused input norm, no norm-backward reduce)
@@ -614,11 +608,11 @@ int conv_k3_which(int mode, int dtype, int ksize, int stride, int B, int Di, int
   return 0;
 }
 
-int conv_k3_launch(int mode, int dtype, int ksize, int stride, ConvArgs& c, void* stream) {
+int conv_k3_launch(int mode, int dtype, int ksize, int stride, ConvArgs& c, void* stream, int* rows) {
   if (!k3_serves(mode, dtype, ksize, stride, c.B, c.Di, c.Hi, c.Wi, c.Do, c.Ho, c.Wo, c.Cin, c.Cout, c.in_mask.m || c.out_mask.m, c.accumulate != 0,
                  c.nb_x != nullptr, c.ep_scale || c.ep_res || c.ep_act != AM_ACT_NONE, c.partials != nullptr)) return 0;
-  int units;
-  const int G = k3_grid(c.B, c.Di, c.Hi, c.Wi, c.Cout, &units);
+  const int dev = am_device();
+  const int units = k3_units(c.B, c.Di, c.Hi, c.Wi, c.Cout), G = k3_grid(units, c.Cout, dev);
 #ifdef AM_ABLATE
   if (getenv("AM_CV_NOK3")) return 0;
   { const char* e_ = getenv("AM_K3_NO32"); if (e_ && atoi(e_) && c.Cout % 64) return 0; }
@@ -627,7 +621,7 @@ int conv_k3_launch(int mode, int dtype, int ksize, int stride, ConvArgs& c, void
   a.x = (const bf16_t*)c.x; a.w = (const bf16_t*)c.w; a.bias = c.bias; a.y = (bf16_t*)c.y; a.partials = c.partials;
   a.ep_scale = c.ep_scale; a.ep_shift = c.ep_shift; a.ep_res = (const bf16_t*)c.ep_res; a.ep_act = c.ep_act;
   a.B = c.B; a.D = c.Di; a.H = c.Hi; a.W = c.Wi; a.Cin = c.Cin; a.Cout = c.Cout; a.Cinp = c.Cinp; a.Coutp = c.Coutp;
-  a.nbd = c.Di / KBD; a.nbh = c.Hi / KBH; a.nbw = c.Wi / KBW; a.ny = c.Cout % 64 ? c.Cout / 32 : c.Cout / 64; a.nunit = units; a.nslab = c.Cinp / 32;
+  a.nbd = c.Di / KBD; a.nbh = c.Hi / KBH; a.nbw = c.Wi / KBW; a.ny = k3_tiles(c.Cout); a.nunit = units; a.nslab = c.Cinp / 32;
   a.flip = mode == AM_CONV_DGRAD;
   a.nt_store = (size_t)c.B * c.Do * c.Ho * c.Wo * c.Cout * 2 >= ((size_t)384 << 20);
   a.w_bytes = (unsigned)c.w_bytes;
@@ -638,19 +632,12 @@ int conv_k3_launch(int mode, int dtype, int ksize, int stride, ConvArgs& c, void
   auto kern = ep ? conv_k3_kernel<4, true, false> : (a.partials ? conv_k3_kernel<4, false, true> : conv_k3_kernel<4, false, false>);
   if (c.Cout % 64) kern = ep ? conv_k3_kernel<2, true, false> : (a.partials ? conv_k3_kernel<2, false, true> : conv_k3_kernel<2, false, false>);
   else if (a.partials && !ep && c.stats_sum_only) kern = conv_k3_kernel<4, false, true, false, true>;      // (the rows' sum-of-squares column stays zero)
-  {
-    static PerDeviceOnce lds_cap; static int optin_err = 0;
-    lds_cap.run([&](int) {
-      const void* ks[7] = {(const void*)conv_k3_kernel<4, true, false>, (const void*)conv_k3_kernel<4, false, true>, (const void*)conv_k3_kernel<4, false, false>,
-                           (const void*)conv_k3_kernel<2, true, false>, (const void*)conv_k3_kernel<2, false, true>, (const void*)conv_k3_kernel<2, false, false>,
-                           (const void*)conv_k3_kernel<4, false, true, false, true>};
-      for (const void* kp : ks) { hipError_t e_ = hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); if (e_ != hipSuccess) optin_err = (int)e_; }
-      (void)hipGetLastError();
-    });
-    if (optin_err) return AM_STAGE_ERR(optin_err);
-  }
+  AM_HIP_STAGE((am_lds_optin<conv_k3_kernel<4, true, false>, conv_k3_kernel<4, false, true>, conv_k3_kernel<4, false, false>,
+                             conv_k3_kernel<2, true, false>, conv_k3_kernel<2, false, true>, conv_k3_kernel<2, false, false>,
+                             conv_k3_kernel<4, false, true, false, true>>(dev)));
   AM_LAUNCH(kern, dim3(G), dim3(512), KLDS, (hipStream_t)stream, a);
   AM_CHECK_LAUNCH_STAGE();
+  if (rows) *rows = G * 8;
   return 1;
 }
 
@@ -658,8 +645,8 @@ int conv_k3_launch(int mode, int dtype, int ksize, int stride, ConvArgs& c, void
 int conv_k3t_launch(int mode, int dtype, int ksize, int stride, ConvArgs& c, void* stream) {
   if (!k3t_serves(mode, dtype, ksize, stride, c.B, c.Di, c.Hi, c.Wi, c.Do, c.Ho, c.Wo, c.Cin, c.Cout, c.in_mask.m || c.out_mask.m, c.accumulate != 0,
                   c.nb_x != nullptr, c.ep_scale || c.ep_res || c.ep_act != AM_ACT_NONE, c.partials != nullptr)) return 0;
-  int units;
-  const int G = k3_grid(c.B, c.Di, c.Hi, c.Wi, c.Cout, &units);          // units = bricks x channel tiles (the eight classes live inside a unit)
+  const int dev = am_device();
+  const int units = k3_units(c.B, c.Di, c.Hi, c.Wi, c.Cout), G = k3_grid(units, c.Cout, dev);
 #ifdef AM_ABLATE
   { const char* e_ = getenv("AM_CV_NOK3T"); if (e_ && atoi(e_)) return 0; }
 #endif
@@ -674,8 +661,8 @@ int conv_k3t_launch(int mode, int dtype, int ksize, int stride, ConvArgs& c, voi
 #ifdef AM_ABLATE
   { const char* e = getenv("AM_K3_DBG"); a.dbg = e ? atoi(e) : 0; }
 #endif
-  auto kern = conv_k3_kernel<4, false, false, true>;
-  AM_LDS_OPTIN_STAGE(kern);
+  constexpr auto kern = conv_k3_kernel<4, false, false, true>;
+  AM_HIP_STAGE(am_lds_optin<kern>(dev));
   AM_LAUNCH(kern, dim3(G), dim3(512), KLDS, (hipStream_t)stream, a);
   AM_CHECK_LAUNCH_STAGE();
   return 1;

@@ -42,14 +42,6 @@ struct ConvArgs {
 #endif
 };
 
-// Ablation switches exist only in the tools build (anatomask_amd.build --ablate -> libanatomask_hip_ablate.so); in the product
-// library AM_DBG() is the constant false and no environment variable is ever read.
-#ifdef AM_ABLATE
-#define AM_DBG(a_, bit_) (((a_).dbg & (bit_)) != 0)
-#else
-#define AM_DBG(a_, bit_) false
-#endif
-
 constexpr int ROWB = 64;      // channel-slab bytes staged per voxel / per weight row (unpadded, XOR-swizzled)
 constexpr int LROWB = 80;     // LDS row stride of the source brick (16 B pad; B-fragment address = lane const + scalar tap offset)
 // taps per weight group staged in LDS (TGS = 3: ~48 MFMAs per wave between barriers).  Multi-unit plans (strided / transposed:
@@ -60,11 +52,6 @@ constexpr int TG_OF(int ns, int tgs) { return ns == 2 ? 2 * tgs : tgs; }
 // With this swizzle a ds_read_b128 of 16 consecutive rows (any alignment) x 4 chunks is bank-conflict free
 // (brute-forced over the four 16-lane groups of the instruction, MI355X_MICROARCH.md "LDS").
 __device__ __forceinline__ int swz(int row, int chunk) { return (row << 6) + ((chunk ^ ((row >> 1) & 2)) << 4); }
-
-// MFMA tile row -> output channel.  D row 4g+r of cout tile i lands in lane group g, register r; rows are assigned so that
-// a lane's registers of tiles (2h, 2h+1) are the 8 CONSECUTIVE channels h*32 + g*8 .. +8: the epilogue stores 16 bytes per
-// lane and the 4 lane groups of a voxel write one contiguous 64-byte run (instead of 8-byte pieces of four 32-byte runs).
-__device__ __forceinline__ int crow(int R) { return ((R >> 5) << 5) + (((R >> 2) & 3) << 3) + (((R >> 4) & 1) << 2) + (R & 3); }
 
 
 // host: tap tables ------------------------------------------------------------------------------
@@ -148,8 +135,9 @@ int conv_gather_rows(int mode, int dtype, int ksize, int stride, int B, int Do, 
                      int n_active);   // partial-sum rows such a launch writes, or 0 when the shape does not qualify
 
 // dense k3 s1 forward / data gradient, bf16, persistent 8-wave LDS-DMA kernel (conv_k3.hip): 1 when it took the launch, 0 when the shape
-// does not qualify; conv_k3_rows = the partial-sum rows such a launch writes (8 per workgroup), or 0
-int conv_k3_launch(int mode, int dtype, int ksize, int stride, ConvArgs& a, void* stream);
+// does not qualify; conv_k3_rows = the partial-sum rows such a launch writes on the current device (8 per workgroup), or 0 -- a launch
+// that was served leaves the same number in *rows
+int conv_k3_launch(int mode, int dtype, int ksize, int stride, ConvArgs& a, void* stream, int* rows);
 int conv_k3_rows(int mode, int dtype, int ksize, int stride, int B, int D, int H, int W, int Cin, int Cout, int masks);
 int conv_k3t_launch(int mode, int dtype, int ksize, int stride, ConvArgs& c, void* stream);   // ConvTranspose3d k4 s2 p1 on the same kernel
 // which of the two serves an am_conv3d launch of this shape and these options (0 neither, 1 conv_k3_kernel, 2 its transposed instantiation):

@@ -440,8 +440,8 @@ bool rw_geometry(RwGeo& G, int mode, int dtype, int k, int stride, int B, int Do
 
 template <int NW, int BD, int BH, int BW, int NS, int NIT, bool HR, int LR>
 int rw_launch(ConvArgs& a, RwArgs& r, const RwGeo& G, size_t lds, hipStream_t st) {
-  auto kern = conv_rw_kernel<NW, BD, BH, BW, NS, NIT, HR, LR>;
-  AM_LDS_OPTIN_STAGE(kern);
+  constexpr auto kern = conv_rw_kernel<NW, BD, BH, BW, NS, NIT, HR, LR>;
+  AM_HIP_STAGE(am_lds_optin<kern>());
   dim3 grid(G.nwg, (a.Cout + 16 * NS - 1) / (16 * NS), 1);
   AM_LAUNCH(kern, grid, dim3(NW * 64), lds, st, a, r);
   AM_CHECK_LAUNCH_STAGE();

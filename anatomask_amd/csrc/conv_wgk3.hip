@@ -354,11 +354,8 @@ int conv_wgk3_launch(const void* x, const void* dy, float* dw, int B, int D, int
 #ifdef AM_ABLATE
   { const char* e_ = getenv("AM_WG_NOK3"); if (e_ && atoi(e_)) return 0; }
 #endif
-  static PerDeviceOnce cu_once; static int cus_of[64];     // per device (ordinal & 63, as PerDeviceOnce keys it): the slot count follows the device that launches
-  int dev_ = 0; (void)hipGetDevice(&dev_);
-  cu_once.run([&](int d) { hipDeviceProp_t pr; cus_of[d & 63] = (hipGetDeviceProperties(&pr, d) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256; (void)hipGetLastError(); });
-  const int cus_cached = cus_of[dev_ & 63] > 0 ? cus_of[dev_ & 63] : 256;
-  const int cap = cus_cached / 8 > 0 ? cus_cached / 8 : 1;   // resident workgroups per XCD: one per CU
+  const int dev = am_device();                             // the slot count follows the device that launches
+  const int cap = am_cu_count(dev) / 8 > 0 ? am_cu_count(dev) / 8 : 1;   // resident workgroups per XCD: one per CU
   Wk3Args a;
   a.x = (const bf16_t*)x; a.dy = (const bf16_t*)dy; a.dw = dw;
   a.B = B; a.D = D; a.H = H; a.W = W; a.Cx = Cx; a.Cy = Cy; a.nbh = nbh; a.nbw = nbw;
@@ -398,8 +395,7 @@ int conv_wgk3_launch(const void* x, const void* dy, float* dw, int B, int D, int
 #ifdef AM_ABLATE
   { const char* e_ = getenv("AM_WGK3_DBG"); a.dbg = e_ ? atoi(e_) : 0; }
 #endif
-  AM_LDS_OPTIN_STAGE(wgrad_k3_kernel<4>);
-  AM_LDS_OPTIN_STAGE(wgrad_k3_kernel<2>);
+  AM_HIP_STAGE((am_lds_optin<wgrad_k3_kernel<4>, wgrad_k3_kernel<2>>(dev)));
   if (wide) AM_LAUNCH(wgrad_k3_kernel<4>, dim3((unsigned)(a.split * nsib)), dim3(512), WkGeo<4>::LDS, (hipStream_t)stream, a);
   else AM_LAUNCH(wgrad_k3_kernel<2>, dim3((unsigned)(a.split * nsib)), dim3(512), WkGeo<2>::LDS, (hipStream_t)stream, a);
   AM_CHECK_LAUNCH_STAGE();

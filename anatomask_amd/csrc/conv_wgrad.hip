@@ -59,26 +59,11 @@ struct WgArgs {
   int dbg;                    // tools-only build (-DAM_ABLATE): AM_WG_DBG ablation bits, 1 no flush, 2 no contraction, 4 no global loads, 8 no LDS staging writes
 #endif
 };
-#ifdef AM_ABLATE
-#define AM_DBG(a_, bit_) (((a_).dbg & (bit_)) != 0)
-#else
-#define AM_DBG(a_, bit_) false
-#endif
-
 
 #ifdef AM_ABLATE
 inline bool mi_is4(int Cx, int Cy) { return Cx > 32 && Cy > 32; }
 inline bool wg_dma() { const char* e_ = getenv("AM_WG_DMA"); return e_ && atoi(e_); }     // tools-only build: the LDS-DMA plane-brick variant (same-process A/B)
 #endif
-
-inline int wg_slots(int occ) {                    // resident workgroups of the CURRENT device (CU count cached per device)
-  static int ncu[64];
-  static PerDeviceOnce once;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  once.run([&](int d) { int n = 0; if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || n <= 0) n = 256; ncu[d & 63] = n; (void)hipGetLastError(); });
-  return occ * ncu[dev & 63];
-}
 
 __device__ __forceinline__ s16x4 tr_read(const unsigned char* p) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
@@ -593,7 +578,7 @@ constexpr int AM_WG_ROUNDS = 2;
 
 template <typename T, int BD, int BH, int BW, int NTAP, int NITX, int MI = 4, int NWX = 4, bool S2 = false, bool PF = false, bool DMA = false>
 int launch(WgArgs& a, size_t maxvox, int tiles, int nbrick, int det_slots, hipStream_t st) {
-  auto kern = conv_wgrad_kernel<T, BD, BH, BW, NTAP, NITX, MI, NWX, S2, PF, DMA>;
+  constexpr auto kern = conv_wgrad_kernel<T, BD, BH, BW, NTAP, NITX, MI, NWX, S2, PF, DMA>;
   constexpr size_t RP = sizeof(T) == 2 ? 32 : 16;
   constexpr int CT = 16 * MI, KT = 16 * NWX;
   size_t lds = (size_t)BD * BH * BW * (CT * sizeof(T) + RP) + maxvox * (KT * sizeof(T) + RP);
@@ -619,20 +604,21 @@ int launch(WgArgs& a, size_t maxvox, int tiles, int nbrick, int det_slots, hipSt
   }
   if (lds > 160 * 1024) return -3;
   if (maxvox * (KT / TT<T>::EPC) > (size_t)NITX * 256) return -3;
-  static PerDeviceOnce lds_cap;                   // per instantiation and device
-  static int regs_occ = 2;                        // resident workgroups per CU the register file allows (LDS is accounted per launch; a property of the code object, the same on every gfx950)
-  lds_cap.run([&](int) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  const int dev = am_device();
+  AM_HIP(am_lds_optin<kern>(dev));
+  // resident workgroups per CU the register file allows (LDS is accounted per launch); 2 when the runtime does not say
+  const int regs_occ = am_per_device([](int) {
     int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)kern, 256, 0) == hipSuccess && nb > 0) regs_occ = nb;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)kern, 256, 0) != hipSuccess || nb <= 0) nb = 2;
     (void)hipGetLastError();
-  });
+    return nb;
+  }, dev);
   int occ = (int)((size_t)160 * 1024 / lds);
   if (occ > regs_occ) occ = regs_occ;
   if (occ < 1) occ = 1;
   // Workgroup ids go round-robin over the 8 XCDs and gridDim.x is a multiple of 8, so XCD x runs the slots with slot % 8 == x, times
   // `tiles`: choose slots-per-XCD so that no XCD gets one workgroup more than R whole rounds of its resident set
-  int cap = wg_slots(occ) / 8;                             // resident workgroups per XCD
+  int cap = occ * am_cu_count(dev) / 8;                    // resident workgroups per XCD of the device that launches
 #ifdef AM_ABLATE
   { const char* e_ = getenv("AM_WG_SPARE"); if (e_ && atoi(e_) > 0 && cap > atoi(e_)) cap -= atoi(e_); }   // tools: leave slots free for the other stream's small kernels
 #endif
@@ -1023,7 +1009,14 @@ extern "C" int am_conv3d_wgrad(int mode, int dtype, int ksize, int stride, const
     const int tiles = ((Cy + 16 * mi - 1) / (16 * mi)) * ((Cx + 16 * nwx - 1) / (16 * nwx)) * a.ngroup;
     a.plist = plist0; a.nlive = plist0 ? n_active : 0; a.pbd = a.pbh = a.pbw = 1;      // (launch() turns patches into live bricks of ITS brick shape)
     int rc = -2;
-#define WG_CASE(TT_, BH_, BW_, NT_, NX_) rc = launch<TT_, 2, BH_, BW_, NT_, NX_>(a, maxvox, tiles, nbrick, det_slots, st)
+    // two-plane bricks of bh x bw voxels: the tap count picks the instantiation (NITX: 7 staging iterations for nine taps, 8 below; fp32 13 / 16)
+    const auto two_plane = [&](auto t, auto bh_, auto bw_) {
+      using T = typename decltype(t)::type;
+      am_by_int<9, 8, 4, 2, 1>(ntap, [&](auto nt) {
+        constexpr int nitx = sizeof(T) == 2 ? (nt == 9 ? 7 : 8) : (nt == 9 ? 13 : 16);
+        rc = launch<T, 2, bh_, bw_, nt, nitx>(a, maxvox, tiles, nbrick, det_slots, st);
+      });
+    };
     if (s2full) rc = bw == 8 ? launch<bf16_t, 1, 8, 8, 9, 5, 4, 2, true, true>(a, maxvox, tiles, nbrick, det_slots, st)
                              : launch<bf16_t, 1, 4, 16, 9, 5, 4, 2, true, true>(a, maxvox, tiles, nbrick, det_slots, st);
     else if (bf && bd == 1 && ntap == 9 && (mi == 2 || nwx == 2)) {
@@ -1050,16 +1043,12 @@ extern "C" int am_conv3d_wgrad(int mode, int dtype, int ksize, int stride, const
       else
 #endif
       if (ntap == 9 && bd == 1) rc = launch<bf16_t, 1, 8, 16, 9, 6>(a, maxvox, tiles, nbrick, det_slots, st);
-      else if (ntap == 9) WG_CASE(bf16_t, 4, 16, 9, 7); else if (ntap == 8) WG_CASE(bf16_t, 4, 16, 8, 8); else if (ntap == 4) WG_CASE(bf16_t, 4, 16, 4, 8);
-      else if (ntap == 2) WG_CASE(bf16_t, 4, 16, 2, 8); else WG_CASE(bf16_t, 4, 16, 1, 8);
+      else two_plane(am_type<bf16_t>{}, am_int<4>{}, am_int<16>{});
     } else if (bf) {
-      if (ntap == 9) WG_CASE(bf16_t, 8, 8, 9, 7); else if (ntap == 8) WG_CASE(bf16_t, 8, 8, 8, 8); else if (ntap == 4) WG_CASE(bf16_t, 8, 8, 4, 8);
-      else if (ntap == 2) WG_CASE(bf16_t, 8, 8, 2, 8); else WG_CASE(bf16_t, 8, 8, 1, 8);
+      two_plane(am_type<bf16_t>{}, am_int<8>{}, am_int<8>{});
     } else {
-      if (ntap == 9) WG_CASE(float, 8, 8, 9, 13); else if (ntap == 8) WG_CASE(float, 8, 8, 8, 16); else if (ntap == 4) WG_CASE(float, 8, 8, 4, 16);
-      else if (ntap == 2) WG_CASE(float, 8, 8, 2, 16); else WG_CASE(float, 8, 8, 1, 16);
+      two_plane(am_type<float>{}, am_int<8>{}, am_int<8>{});
     }
-#undef WG_CASE
     if (rc) return rc;
   }
   return 0;

@@ -201,9 +201,8 @@ __global__ void head_fold_kernel(const float* __restrict__ w2, int cmid, int cin
 template <typename T, int NCH> int hs_launch(const HsArgs& a, hipStream_t st) {
   constexpr int NW = HK<T>::NW;
   const size_t lds = (size_t)HNT * 16 * HPS * 4 + (size_t)NCH * 2 * NW * 1024 + 16;
-  auto kern = head_stencil_kernel<T, NCH>;
-  static PerDeviceOnce once;
-  once.run([&](int) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); (void)hipGetLastError(); });
+  constexpr auto kern = head_stencil_kernel<T, NCH>;
+  AM_HIP(am_lds_optin<kern>());
   AM_LAUNCH(kern, dim3((unsigned)a.npatch), dim3(256), lds, st, a);
   AM_CHECK_LAUNCH();
   return 0;

@@ -770,15 +770,44 @@ inline bool list_ok(const uint8_t* mask, const int* plist, int n_active) { retur
 
 }  // namespace
 
-#define DISPATCH_T(dtype, CALL_F32, CALL_BF16) do { if ((dtype) == AM_DT_BF16) { CALL_BF16; } else { CALL_F32; } } while (0)
-// (a voxel row must fit the 256 threads of a workgroup as 16-byte chunks: C <= 2048 in bf16, C <= 1024 in fp32 -- refuse, never mis-compute)
-#define CHK_C(C) do { if ((C) % 8 || (C) > 2048 || (C) <= 0 || (dtype != AM_DT_BF16 && (C) > 1024)) return -1; } while (0)
+// every entry point here launches 256 threads: fp32 rows up to 1024 channels (am_row_ok)
+constexpr int F32_MAX_C = 1024;
+
+namespace {
+template <typename T, int K>
+int launch_dw(const void* x, const float* w, const float* bias, void* y, int B, int D, int H, int W, int C, MaskView mv, int flip, hipStream_t st) {
+  constexpr int EPC = TT<T>::EPC;
+  constexpr auto kern = dwconv_kernel<T, K>;
+  const size_t sm = (size_t)(DWD + K - 1) * (DWH + K - 1) * (DWW + K - 1) * 16 + (size_t)K * K * K * EPC * 4;
+  AM_HIP(am_lds_optin<kern>());
+  const int nbrick = B * ((D + DWD - 1) / DWD) * ((H + DWH - 1) / DWH) * ((W + DWW - 1) / DWW);
+  AM_LAUNCH(kern, dim3((unsigned)((nbrick + 7) / 8 * 8 * (C / EPC))), dim3(256), sm, st, (const T*)x, w, bias, (T*)y, B, D, H, W, C, mv, flip);
+  AM_CHECK_LAUNCH();
+  return 0;
+}
+template <typename T, int K>
+int launch_dw_wgrad(const void* x, const void* dy, float* dw, float* db, int B, int D, int H, int W, int C, MaskView mv, hipStream_t st) {
+  constexpr int EPC = TT<T>::EPC;
+  constexpr auto kern = dwconv_wgrad_kernel<T, K>;
+  size_t sm = ((size_t)(DWD + K - 1) * (DWH + K - 1) * (DWW + K - 1) + (size_t)DWD * DWH * DWW) * 16;
+  const size_t fold = (size_t)(4 * 64 * K * EPC + 4 * (64 / (K * K)) * EPC) * 4;
+  if (sm < fold) sm = fold;
+  AM_HIP(am_lds_optin<kern>());
+  const int nbrick = B * ((D + DWD - 1) / DWD) * ((H + DWH - 1) / DWH) * ((W + DWW - 1) / DWW);
+  int nslot = 1024 / (C / EPC) / 8 * 8;                       // ~four workgroups per CU over all channel chunks, a multiple of 8
+  if (nslot < 8) nslot = 8;
+  if (nslot > (nbrick + 7) / 8 * 8) nslot = (nbrick + 7) / 8 * 8;
+  AM_LAUNCH(kern, dim3((unsigned)(nslot * (C / EPC))), dim3(256), sm, st, (const T*)x, (const T*)dy, dw, db, B, D, H, W, C, mv, nslot);
+  AM_CHECK_LAUNCH();
+  return 0;
+}
+}  // namespace
 
 extern "C" {
 
 int am_voxel_norm_fwd(int dtype, int kind, const void* x, void* y, int B, int D, int H, int W, int C, int groups, const float* gamma,
                       const float* beta, float eps, const uint8_t* mask, int bshift, const int32_t* active_list, int n_active, void* stream) {
-  CHK_C(C);
+  if (!am_row_ok(dtype, C, F32_MAX_C)) return -1;
   if (!gamma || groups < 1 || C % groups || (kind != 0 && kind != 1)) return -1;
   if (!list_ok(mask, active_list, n_active)) return -2;         // block-sparse tensors are walked through their active-patch list
   const int epc = dtype == AM_DT_BF16 ? 8 : 4;
@@ -789,12 +818,10 @@ int am_voxel_norm_fwd(int dtype, int kind, const void* x, void* y, int B, int D,
   const int nv = 256 / (C / epc);
   const int nb = nblocks((g.nvox + nv - 1) / nv * 256);
   hipStream_t st = (hipStream_t)stream;
-  if (kind == 0)
-    DISPATCH_T(dtype, AM_LAUNCH((voxel_norm_fwd_kernel<float, VN_GROUP>), dim3(nb), dim3(256), 0, st, (const float*)x, (float*)y, g, cg, gamma, beta, eps),
-               AM_LAUNCH((voxel_norm_fwd_kernel<bf16_t, VN_GROUP>), dim3(nb), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)y, g, cg, gamma, beta, eps));
-  else
-    DISPATCH_T(dtype, AM_LAUNCH((voxel_norm_fwd_kernel<float, VN_GRN>), dim3(nb), dim3(256), 0, st, (const float*)x, (float*)y, g, cg, gamma, beta, eps),
-               AM_LAUNCH((voxel_norm_fwd_kernel<bf16_t, VN_GRN>), dim3(nb), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)y, g, cg, gamma, beta, eps));
+  am_by_dtype_int<VN_GROUP, VN_GRN>(dtype, kind, [&](auto t, auto mode) {
+    using T = typename decltype(t)::type;
+    AM_LAUNCH((voxel_norm_fwd_kernel<T, mode>), dim3(nb), dim3(256), 0, st, (const T*)x, (T*)y, g, cg, gamma, beta, eps);
+  });
   AM_CHECK_LAUNCH();
   return 0;
 }
@@ -802,7 +829,7 @@ int am_voxel_norm_fwd(int dtype, int kind, const void* x, void* y, int B, int D,
 int am_voxel_norm_bwd(int dtype, int kind, const void* x, const void* dy, void* dx, int B, int D, int H, int W, int C, int groups,
                       const float* gamma, float eps, float* dgamma_accum, float* dbeta_accum, const uint8_t* mask, int bshift,
                       const int32_t* active_list, int n_active, void* stream) {
-  CHK_C(C);
+  if (!am_row_ok(dtype, C, F32_MAX_C)) return -1;
   if (!gamma || groups < 1 || C % groups || (kind != 0 && kind != 1)) return -1;
   if (!list_ok(mask, active_list, n_active)) return -2;
   const int epc = dtype == AM_DT_BF16 ? 8 : 4;
@@ -814,12 +841,10 @@ int am_voxel_norm_bwd(int dtype, int kind, const void* x, const void* dy, void* 
   long nbl = (g.nvox + nv - 1) / nv;
   const int nb = (int)(nbl > 1024 ? 1024 : nbl);                // one atomic flush per workgroup and channel
   hipStream_t st = (hipStream_t)stream;
-  if (kind == 0)
-    DISPATCH_T(dtype, AM_LAUNCH((voxel_norm_bwd_kernel<float, VN_GROUP>), dim3(nb), dim3(256), 0, st, (const float*)x, (const float*)dy, (float*)dx, g, cg, gamma, eps, dgamma_accum, dbeta_accum),
-               AM_LAUNCH((voxel_norm_bwd_kernel<bf16_t, VN_GROUP>), dim3(nb), dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)dx, g, cg, gamma, eps, dgamma_accum, dbeta_accum));
-  else
-    DISPATCH_T(dtype, AM_LAUNCH((voxel_norm_bwd_kernel<float, VN_GRN>), dim3(nb), dim3(256), 0, st, (const float*)x, (const float*)dy, (float*)dx, g, cg, gamma, eps, dgamma_accum, dbeta_accum),
-               AM_LAUNCH((voxel_norm_bwd_kernel<bf16_t, VN_GRN>), dim3(nb), dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)dx, g, cg, gamma, eps, dgamma_accum, dbeta_accum));
+  am_by_dtype_int<VN_GROUP, VN_GRN>(dtype, kind, [&](auto t, auto mode) {
+    using T = typename decltype(t)::type;
+    AM_LAUNCH((voxel_norm_bwd_kernel<T, mode>), dim3(nb), dim3(256), 0, st, (const T*)x, (const T*)dy, (T*)dx, g, cg, gamma, eps, dgamma_accum, dbeta_accum);
+  });
   AM_CHECK_LAUNCH();
   return 0;
 }
@@ -836,7 +861,7 @@ static int pool_out(int n, int k, int s, int p, int dil, int ceil_mode) {
 int am_pool3d_fwd(int dtype, int op, const void* x, void* y, int32_t* argmax, int B, int Di, int Hi, int Wi, int C, int ksize, int stride,
                   int pad, int dilation, int count_include_pad, int Do, int Ho, int Wo, const uint8_t* mask, int in_bshift, int out_bshift,
                   int fd, int fh, int fw, const int32_t* active_list, int n_active, void* stream) {
-  CHK_C(C);
+  if (!am_row_ok(dtype, C, F32_MAX_C)) return -1;
   if ((op != 0 && op != 1) || ksize < 1 || ksize > 7 || stride < 1 || pad < 0 || 2 * pad > ksize || dilation < 1 || (op == 1 && dilation != 1)) return -2;
   {                                                        // (Do, Ho, Wo) = torch's floor OR ceil_mode extents, all three by the same rule
     bool okf = Do == pool_out(Di, ksize, stride, pad, dilation, 0) && Ho == pool_out(Hi, ksize, stride, pad, dilation, 0) && Wo == pool_out(Wi, ksize, stride, pad, dilation, 0);
@@ -850,12 +875,10 @@ int am_pool3d_fwd(int dtype, int op, const void* x, void* y, int32_t* argmax, in
   const int epc = dtype == AM_DT_BF16 ? 8 : 4;
   const int nb = nblocks(go.nvox * (C / epc));
   hipStream_t st = (hipStream_t)stream;
-  if (op == 0)
-    DISPATCH_T(dtype, AM_LAUNCH((pool3d_fwd_kernel<float, 0>), dim3(nb), dim3(256), 0, st, (const float*)x, (float*)y, argmax, go, Di, Hi, Wi, ksize, stride, pad, dilation, count_include_pad, mi),
-               AM_LAUNCH((pool3d_fwd_kernel<bf16_t, 0>), dim3(nb), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)y, argmax, go, Di, Hi, Wi, ksize, stride, pad, dilation, count_include_pad, mi));
-  else
-    DISPATCH_T(dtype, AM_LAUNCH((pool3d_fwd_kernel<float, 1>), dim3(nb), dim3(256), 0, st, (const float*)x, (float*)y, argmax, go, Di, Hi, Wi, ksize, stride, pad, dilation, count_include_pad, mi),
-               AM_LAUNCH((pool3d_fwd_kernel<bf16_t, 1>), dim3(nb), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)y, argmax, go, Di, Hi, Wi, ksize, stride, pad, dilation, count_include_pad, mi));
+  am_by_dtype_int<0, 1>(dtype, op, [&](auto t, auto o) {
+    using T = typename decltype(t)::type;
+    AM_LAUNCH((pool3d_fwd_kernel<T, o>), dim3(nb), dim3(256), 0, st, (const T*)x, (T*)y, argmax, go, Di, Hi, Wi, ksize, stride, pad, dilation, count_include_pad, mi);
+  });
   AM_CHECK_LAUNCH();
   return 0;
 }
@@ -863,7 +886,7 @@ int am_pool3d_fwd(int dtype, int op, const void* x, void* y, int32_t* argmax, in
 int am_pool3d_bwd(int dtype, int op, const void* dy, const int32_t* argmax, void* dx, int B, int Di, int Hi, int Wi, int C, int ksize,
                   int stride, int pad, int dilation, int count_include_pad, int Do, int Ho, int Wo, const uint8_t* mask, int in_bshift,
                   int out_bshift, int fd, int fh, int fw, const int32_t* active_list, int n_active, void* stream) {
-  CHK_C(C);
+  if (!am_row_ok(dtype, C, F32_MAX_C)) return -1;
   if ((op != 0 && op != 1) || (op == 0 && !argmax) || ksize < 1 || ksize > 7 || stride < 1 || dilation < 1 || (op == 1 && dilation != 1)) return -2;
   if (!list_ok(mask, active_list, n_active)) return -2;
   const VoxGeo gi = mkvox(B, Di, Hi, Wi, C, mask ? active_list : nullptr, n_active, in_bshift);
@@ -872,82 +895,40 @@ int am_pool3d_bwd(int dtype, int op, const void* dy, const int32_t* argmax, void
   const int epc = dtype == AM_DT_BF16 ? 8 : 4;
   const int nb = nblocks(gi.nvox * (C / epc));
   hipStream_t st = (hipStream_t)stream;
-  if (op == 0)
-    DISPATCH_T(dtype, AM_LAUNCH((pool3d_bwd_kernel<float, 0>), dim3(nb), dim3(256), 0, st, (const float*)dy, argmax, (float*)dx, gi, Do, Ho, Wo, ksize, stride, pad, dilation, count_include_pad, mo),
-               AM_LAUNCH((pool3d_bwd_kernel<bf16_t, 0>), dim3(nb), dim3(256), 0, st, (const bf16_t*)dy, argmax, (bf16_t*)dx, gi, Do, Ho, Wo, ksize, stride, pad, dilation, count_include_pad, mo));
-  else
-    DISPATCH_T(dtype, AM_LAUNCH((pool3d_bwd_kernel<float, 1>), dim3(nb), dim3(256), 0, st, (const float*)dy, argmax, (float*)dx, gi, Do, Ho, Wo, ksize, stride, pad, dilation, count_include_pad, mo),
-               AM_LAUNCH((pool3d_bwd_kernel<bf16_t, 1>), dim3(nb), dim3(256), 0, st, (const bf16_t*)dy, argmax, (bf16_t*)dx, gi, Do, Ho, Wo, ksize, stride, pad, dilation, count_include_pad, mo));
+  am_by_dtype_int<0, 1>(dtype, op, [&](auto t, auto o) {
+    using T = typename decltype(t)::type;
+    AM_LAUNCH((pool3d_bwd_kernel<T, o>), dim3(nb), dim3(256), 0, st, (const T*)dy, argmax, (T*)dx, gi, Do, Ho, Wo, ksize, stride, pad, dilation, count_include_pad, mo);
+  });
   AM_CHECK_LAUNCH();
   return 0;
 }
-
-}  // extern "C"
-
-namespace {
-template <typename T, int K>
-int launch_dw(const void* x, const float* w, const float* bias, void* y, int B, int D, int H, int W, int C, MaskView mv, int flip, hipStream_t st) {
-  constexpr int EPC = TT<T>::EPC;
-  auto kern = dwconv_kernel<T, K>;
-  const size_t sm = (size_t)(DWD + K - 1) * (DWH + K - 1) * (DWW + K - 1) * 16 + (size_t)K * K * K * EPC * 4;
-  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  const int nbrick = B * ((D + DWD - 1) / DWD) * ((H + DWH - 1) / DWH) * ((W + DWW - 1) / DWW);
-  AM_LAUNCH(kern, dim3((unsigned)((nbrick + 7) / 8 * 8 * (C / EPC))), dim3(256), sm, st, (const T*)x, w, bias, (T*)y, B, D, H, W, C, mv, flip);
-  AM_CHECK_LAUNCH();
-  return 0;
-}
-template <typename T, int K>
-int launch_dw_wgrad(const void* x, const void* dy, float* dw, float* db, int B, int D, int H, int W, int C, MaskView mv, hipStream_t st) {
-  constexpr int EPC = TT<T>::EPC;
-  auto kern = dwconv_wgrad_kernel<T, K>;
-  size_t sm = ((size_t)(DWD + K - 1) * (DWH + K - 1) * (DWW + K - 1) + (size_t)DWD * DWH * DWW) * 16;
-  const size_t fold = (size_t)(4 * 64 * K * EPC + 4 * (64 / (K * K)) * EPC) * 4;
-  if (sm < fold) sm = fold;
-  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  const int nbrick = B * ((D + DWD - 1) / DWD) * ((H + DWH - 1) / DWH) * ((W + DWW - 1) / DWW);
-  int nslot = 1024 / (C / EPC) / 8 * 8;                       // ~four workgroups per CU over all channel chunks, a multiple of 8
-  if (nslot < 8) nslot = 8;
-  if (nslot > (nbrick + 7) / 8 * 8) nslot = (nbrick + 7) / 8 * 8;
-  AM_LAUNCH(kern, dim3((unsigned)(nslot * (C / EPC))), dim3(256), sm, st, (const T*)x, (const T*)dy, dw, db, B, D, H, W, C, mv, nslot);
-  AM_CHECK_LAUNCH();
-  return 0;
-}
-}  // namespace
-
-extern "C" {
 
 int am_dwconv3d(int dtype, int data_grad, const void* x, const float* w, const float* bias, void* y, int B, int D, int H, int W, int C,
                 int ksize, const uint8_t* mask, int bshift, int fd, int fh, int fw, void* stream) {
-  CHK_C(C);
+  if (!am_row_ok(dtype, C, F32_MAX_C)) return -1;
   const MaskView mv{mask, fd, fh, fw, bshift};
-  hipStream_t st = (hipStream_t)stream;
-  const bool bf = dtype == AM_DT_BF16;
-  switch (ksize) {
-    case 3: return bf ? launch_dw<bf16_t, 3>(x, w, bias, y, B, D, H, W, C, mv, data_grad, st) : launch_dw<float, 3>(x, w, bias, y, B, D, H, W, C, mv, data_grad, st);
-    case 5: return bf ? launch_dw<bf16_t, 5>(x, w, bias, y, B, D, H, W, C, mv, data_grad, st) : launch_dw<float, 5>(x, w, bias, y, B, D, H, W, C, mv, data_grad, st);
-    case 7: return bf ? launch_dw<bf16_t, 7>(x, w, bias, y, B, D, H, W, C, mv, data_grad, st) : launch_dw<float, 7>(x, w, bias, y, B, D, H, W, C, mv, data_grad, st);
-    default: return -2;
-  }
+  int rc = -2;                                             // (no kernel of that size)
+  am_by_dtype_int<3, 5, 7>(dtype, ksize, [&](auto t, auto k) {
+    rc = launch_dw<typename decltype(t)::type, k>(x, w, bias, y, B, D, H, W, C, mv, data_grad, (hipStream_t)stream);
+  });
+  return rc;
 }
 
 int am_dwconv3d_wgrad(int dtype, const void* x, const void* dy, float* dw_accum, float* db_accum, int B, int D, int H, int W, int C, int ksize,
                       const uint8_t* mask, int bshift, int fd, int fh, int fw, void* stream) {
-  CHK_C(C);
+  if (!am_row_ok(dtype, C, F32_MAX_C)) return -1;
   const MaskView mv{mask, fd, fh, fw, bshift};
-  hipStream_t st = (hipStream_t)stream;
-  const bool bf = dtype == AM_DT_BF16;
-  switch (ksize) {
-    case 3: return bf ? launch_dw_wgrad<bf16_t, 3>(x, dy, dw_accum, db_accum, B, D, H, W, C, mv, st) : launch_dw_wgrad<float, 3>(x, dy, dw_accum, db_accum, B, D, H, W, C, mv, st);
-    case 5: return bf ? launch_dw_wgrad<bf16_t, 5>(x, dy, dw_accum, db_accum, B, D, H, W, C, mv, st) : launch_dw_wgrad<float, 5>(x, dy, dw_accum, db_accum, B, D, H, W, C, mv, st);
-    case 7: return bf ? launch_dw_wgrad<bf16_t, 7>(x, dy, dw_accum, db_accum, B, D, H, W, C, mv, st) : launch_dw_wgrad<float, 7>(x, dy, dw_accum, db_accum, B, D, H, W, C, mv, st);
-    default: return -2;
-  }
+  int rc = -2;
+  am_by_dtype_int<3, 5, 7>(dtype, ksize, [&](auto t, auto k) {
+    rc = launch_dw_wgrad<typename decltype(t)::type, k>(x, dy, dw_accum, db_accum, B, D, H, W, C, mv, (hipStream_t)stream);
+  });
+  return rc;
 }
 
 int am_dwconv3d_s2(int dtype, int data_grad, const void* src, const float* w, const float* bias, void* dst, int B, int Df, int Hf, int Wf,
                    int C, int ksize, const uint8_t* mask, int fine_bshift, int fd, int fh, int fw, const int32_t* active_list, int n_active,
                    void* stream) {
-  CHK_C(C);
+  if (!am_row_ok(dtype, C, F32_MAX_C)) return -1;
   if (Df % 2 || Hf % 2 || Wf % 2 || (mask && fine_bshift < 1)) return -2;
   if (!list_ok(mask, active_list, n_active)) return -2;
   const int Dc = Df / 2, Hc = Hf / 2, Wc = Wf / 2;
@@ -960,13 +941,13 @@ int am_dwconv3d_s2(int dtype, int data_grad, const void* src, const float* w, co
   const dim3 grid(nblocks(g.nvox), C / epc);
   hipStream_t st = (hipStream_t)stream;
   const int sd = data_grad ? Dc : Df, sh = data_grad ? Hc : Hf, sw = data_grad ? Wc : Wf;
-#define AM_S2(KK)                                                                                                                                   \
-  if (data_grad) DISPATCH_T(dtype, AM_LAUNCH((dwconv_s2_kernel<float, KK, 1>), grid, dim3(256), 0, st, (const float*)src, w, bias, (float*)dst, g, sd, sh, sw, ms), \
-                            AM_LAUNCH((dwconv_s2_kernel<bf16_t, KK, 1>), grid, dim3(256), 0, st, (const bf16_t*)src, w, bias, (bf16_t*)dst, g, sd, sh, sw, ms));     \
-  else DISPATCH_T(dtype, AM_LAUNCH((dwconv_s2_kernel<float, KK, 0>), grid, dim3(256), 0, st, (const float*)src, w, bias, (float*)dst, g, sd, sh, sw, ms),            \
-                  AM_LAUNCH((dwconv_s2_kernel<bf16_t, KK, 0>), grid, dim3(256), 0, st, (const bf16_t*)src, w, bias, (bf16_t*)dst, g, sd, sh, sw, ms))
-  if (ksize == 3) { AM_S2(3); } else if (ksize == 5) { AM_S2(5); } else if (ksize == 7) { AM_S2(7); } else return -2;
-#undef AM_S2
+  const bool known = am_by_dtype_int<3, 5, 7>(dtype, ksize, [&](auto t, auto k) {
+    using T = typename decltype(t)::type;
+    am_by_int<0, 1>(data_grad != 0, [&](auto dg) {
+      AM_LAUNCH((dwconv_s2_kernel<T, k, dg>), grid, dim3(256), 0, st, (const T*)src, w, bias, (T*)dst, g, sd, sh, sw, ms);
+    });
+  });
+  if (!known) return -2;
   AM_CHECK_LAUNCH();
   return 0;
 }
@@ -974,7 +955,7 @@ int am_dwconv3d_s2(int dtype, int data_grad, const void* src, const float* w, co
 int am_dwconv3d_s2_wgrad(int dtype, const void* x, const void* dy, float* dw_accum, float* db_accum, int B, int Df, int Hf, int Wf, int C,
                          int ksize, const uint8_t* mask, int fine_bshift, int fd, int fh, int fw, const int32_t* active_list, int n_active,
                          void* stream) {
-  CHK_C(C);
+  if (!am_row_ok(dtype, C, F32_MAX_C)) return -1;
   if (Df % 2 || Hf % 2 || Wf % 2 || (mask && fine_bshift < 1)) return -2;
   if (!list_ok(mask, active_list, n_active)) return -2;
   const VoxGeo go = mkvox(B, Df / 2, Hf / 2, Wf / 2, C, mask ? active_list : nullptr, n_active, fine_bshift - 1);
@@ -984,37 +965,35 @@ int am_dwconv3d_s2_wgrad(int dtype, const void* x, const void* dy, float* dw_acc
   long per = 2048 / (C / epc); if (per < 1) per = 1; if (per > go.nvox) per = go.nvox;
   const dim3 grid((unsigned)per, C / epc);
   hipStream_t st = (hipStream_t)stream;
-#define AM_S2W(KK)                                                                                                                                   \
-  DISPATCH_T(dtype, AM_LAUNCH((dwconv_s2_wgrad_kernel<float, KK>), grid, dim3(256), 0, st, (const float*)x, (const float*)dy, dw_accum, db_accum, go, Df, Hf, Wf, mx), \
-             AM_LAUNCH((dwconv_s2_wgrad_kernel<bf16_t, KK>), grid, dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)dy, dw_accum, db_accum, go, Df, Hf, Wf, mx))
-  if (ksize == 3) { AM_S2W(3); } else if (ksize == 5) { AM_S2W(5); } else if (ksize == 7) { AM_S2W(7); } else return -2;
-#undef AM_S2W
+  const bool known = am_by_dtype_int<3, 5, 7>(dtype, ksize, [&](auto t, auto k) {
+    using T = typename decltype(t)::type;
+    AM_LAUNCH((dwconv_s2_wgrad_kernel<T, k>), grid, dim3(256), 0, st, (const T*)x, (const T*)dy, dw_accum, db_accum, go, Df, Hf, Wf, mx);
+  });
+  if (!known) return -2;
   AM_CHECK_LAUNCH();
   return 0;
 }
 
 int am_gelu(int dtype, const void* x, const void* dy, void* out, int B, int D, int H, int W, int C, const uint8_t* mask, int bshift,
             const int32_t* active_list, int n_active, void* stream) {
-  CHK_C(C);
+  if (!am_row_ok(dtype, C, F32_MAX_C)) return -1;
   if (!list_ok(mask, active_list, n_active)) return -2;
   const VoxGeo g = mkvox(B, D, H, W, C, mask ? active_list : nullptr, n_active, bshift);
   if (g.nvox == 0) return 0;
   const int epc = dtype == AM_DT_BF16 ? 8 : 4;
   const int nb = nblocks(g.nvox * (C / epc));
   hipStream_t st = (hipStream_t)stream;
-  if (dy)
-    DISPATCH_T(dtype, AM_LAUNCH((gelu_kernel<float, 1>), dim3(nb), dim3(256), 0, st, (const float*)x, (const float*)dy, (float*)out, g),
-               AM_LAUNCH((gelu_kernel<bf16_t, 1>), dim3(nb), dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)out, g));
-  else
-    DISPATCH_T(dtype, AM_LAUNCH((gelu_kernel<float, 0>), dim3(nb), dim3(256), 0, st, (const float*)x, (const float*)nullptr, (float*)out, g),
-               AM_LAUNCH((gelu_kernel<bf16_t, 0>), dim3(nb), dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)nullptr, (bf16_t*)out, g));
+  am_by_dtype_int<0, 1>(dtype, dy != nullptr, [&](auto t, auto bwd) {          // dy: the backward pass
+    using T = typename decltype(t)::type;
+    AM_LAUNCH((gelu_kernel<T, bwd>), dim3(nb), dim3(256), 0, st, (const T*)x, (const T*)dy, (T*)out, g);
+  });
   AM_CHECK_LAUNCH();
   return 0;
 }
 
 int am_scale_residual(int dtype, int backward, const void* x, const void* other, const float* gamma, void* out, float* dgamma_accum, int B, int D,
                       int H, int W, int C, const uint8_t* mask, int bshift, const int32_t* active_list, int n_active, void* stream) {
-  CHK_C(C);
+  if (!am_row_ok(dtype, C, F32_MAX_C)) return -1;
   if (!list_ok(mask, active_list, n_active)) return -2;
   const VoxGeo g = mkvox(B, D, H, W, C, mask ? active_list : nullptr, n_active, bshift);
   if (g.nvox == 0) return 0;
@@ -1023,39 +1002,41 @@ int am_scale_residual(int dtype, int backward, const void* x, const void* other,
   long nbl = (g.nvox + nv - 1) / nv;
   const int nb = (int)(nbl > 2048 ? 2048 : nbl);
   hipStream_t st = (hipStream_t)stream;
-  if (backward)
-    DISPATCH_T(dtype, AM_LAUNCH((scale_residual_kernel<float, 1>), dim3(nb), dim3(256), 0, st, (const float*)x, (const float*)other, gamma, (float*)out, dgamma_accum, g),
-               AM_LAUNCH((scale_residual_kernel<bf16_t, 1>), dim3(nb), dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)other, gamma, (bf16_t*)out, dgamma_accum, g));
-  else
-    DISPATCH_T(dtype, AM_LAUNCH((scale_residual_kernel<float, 0>), dim3(nb), dim3(256), 0, st, (const float*)x, (const float*)other, gamma, (float*)out, dgamma_accum, g),
-               AM_LAUNCH((scale_residual_kernel<bf16_t, 0>), dim3(nb), dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)other, gamma, (bf16_t*)out, dgamma_accum, g));
+  am_by_dtype_int<0, 1>(dtype, backward != 0, [&](auto t, auto bwd) {
+    using T = typename decltype(t)::type;
+    AM_LAUNCH((scale_residual_kernel<T, bwd>), dim3(nb), dim3(256), 0, st, (const T*)x, (const T*)other, gamma, (T*)out, dgamma_accum, g);
+  });
   AM_CHECK_LAUNCH();
   return 0;
 }
 
 int am_masked_mean_fwd(int dtype, const void* x, float* mean, int B, int D, int H, int W, int C, const uint8_t* mask, int bshift, int fd, int fh,
                        int fw, void* stream) {
-  CHK_C(C);
+  if (!am_row_ok(dtype, C, F32_MAX_C)) return -1;
   const MaskView mv{mask, fd, fh, fw, bshift};
   const int epc = dtype == AM_DT_BF16 ? 8 : 4;
   hipStream_t st = (hipStream_t)stream;
-  DISPATCH_T(dtype, AM_LAUNCH(masked_mean_fwd_kernel<float>, dim3(B, C / epc), dim3(256), 0, st, (const float*)x, mean, B, D, H, W, C, mv),
-             AM_LAUNCH(masked_mean_fwd_kernel<bf16_t>, dim3(B, C / epc), dim3(256), 0, st, (const bf16_t*)x, mean, B, D, H, W, C, mv));
+  am_by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    AM_LAUNCH(masked_mean_fwd_kernel<T>, dim3(B, C / epc), dim3(256), 0, st, (const T*)x, mean, B, D, H, W, C, mv);
+  });
   AM_CHECK_LAUNCH();
   return 0;
 }
 
 int am_masked_mean_bwd(int dtype, const float* dmean, const float* count, void* dx, int B, int D, int H, int W, int C, const uint8_t* mask,
                        int bshift, const int32_t* active_list, int n_active, void* stream) {
-  CHK_C(C);
+  if (!am_row_ok(dtype, C, F32_MAX_C)) return -1;
   if (!list_ok(mask, active_list, n_active)) return -2;
   const VoxGeo g = mkvox(B, D, H, W, C, mask ? active_list : nullptr, n_active, bshift);
   if (g.nvox == 0) return 0;
   const int epc = dtype == AM_DT_BF16 ? 8 : 4;
   const int nb = nblocks(g.nvox * (C / epc));
   hipStream_t st = (hipStream_t)stream;
-  DISPATCH_T(dtype, AM_LAUNCH(masked_mean_bwd_kernel<float>, dim3(nb), dim3(256), 0, st, dmean, count, (float*)dx, g),
-             AM_LAUNCH(masked_mean_bwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, st, dmean, count, (bf16_t*)dx, g));
+  am_by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    AM_LAUNCH(masked_mean_bwd_kernel<T>, dim3(nb), dim3(256), 0, st, dmean, count, (T*)dx, g);
+  });
   AM_CHECK_LAUNCH();
   return 0;
 }

@@ -10,10 +10,6 @@
 
 namespace {
 
-// MFMA tile row -> output channel (same permutation as the convolution kernels, conv_plan.h): a lane's registers of tiles (2h, 2h+1)
-// are 8 consecutive channels
-__device__ __forceinline__ int crow(int R) { return ((R >> 5) << 5) + (((R >> 2) & 3) << 3) + (((R >> 4) & 1) << 2) + (R & 3); }
-
 constexpr int NREP = 8;      // replicated reduction accumulators (spreads same-address atomic contention)
 
 struct Geo {                 // a channels-last tensor [B][D][H][W][C] and its (optional) patch mask
@@ -1780,44 +1776,36 @@ inline int rows_threads(const RowGeo& r) { return r.rpp * r.rowchunks; }
 
 }  // namespace
 
-// fp32 launch of a linear (Walk) kernel: 512-thread workgroups when a voxel row has more than 256 chunks (C > 1024)
-#define AM_LAUNCH_F32W(C_, KERN_, GRID_, ST_, ...) do { if ((C_) / 4 > 256) AM_LAUNCH((KERN_<float, 512>), GRID_, dim3(512), 0, ST_, __VA_ARGS__); \
-                                                        else AM_LAUNCH((KERN_<float, 256>), GRID_, dim3(256), 0, ST_, __VA_ARGS__); } while (0)
-#define DISPATCH_T(dtype, CALL_F32, CALL_BF16) do { if ((dtype) == AM_DT_BF16) { CALL_BF16; } else { CALL_F32; } } while (0)
-#define CHK_C(C) do { if ((C) % 8 || (C) > 2048 || (C) <= 0) return -1; } while (0)
-// entry points without a 512-thread instantiation (stem convs, projection head: Walk<T> kernels launched with 256 threads) refuse fp32 rows
-// wider than 1024 channels, as layer_ops.hip does -- with 256 threads such a row leaves every thread idle and the output untouched
-#define CHK_C_NARROW(C) do { CHK_C(C); if (dtype != AM_DT_BF16 && (C) > 1024) return -1; } while (0)
-
-// backward norm kernels: activation x derivative source (saved output / recomputed pre-activation) -> the specialised instantiation
-#define AM_BWD_SPEC(act_, has_out_, M_) do {                                                                        \
-    if ((act_) == AM_ACT_NONE) M_(0, 0);                                                                            \
-    else if ((act_) == AM_ACT_LRELU && (has_out_)) M_(1, 1);                                                        \
-    else if ((act_) == AM_ACT_LRELU) M_(1, 0);                                                                      \
-    else if ((act_) == AM_ACT_RELU6 && (has_out_)) M_(2, 1);                                                        \
-    else if ((act_) == AM_ACT_RELU6) M_(2, 0);                                                                      \
-    else M_(-1, 0); } while (0)
+// fp32 rows: the norm / sum entry points have 512-thread instantiations (am_by_walk) and take up to 2048 channels; the others (stem
+// convolutions, projection head: Walk<T> kernels launched with 256 threads) up to 1024 -- am_row_ok
+constexpr int F32_MAX_C_512 = 2048, F32_MAX_C_256 = 1024;
+// packed weight copies also exist in the split-product layout (AM_DT_F32S)
+template <typename F> inline void by_pack_dtype(int dtype, F&& f) { if (dtype == AM_DT_F32S) f(am_type<f32s_t>{}); else am_by_dtype(dtype, f); }
 
 extern "C" {
 
 int am_chan_stats(int dtype, const void* x, int B, int D, int H, int W, int C, const uint8_t* mask, int bshift, int fd, int fh,
                   int fw, double* sums, const int32_t* active_list, int n_active, void* stream) {
-  CHK_C(C);
+  if (!am_row_ok(dtype, C, F32_MAX_C_512)) return -1;
   Geo g = mkgeo(dtype, true, B, D, H, W, C, mask, bshift, fd, fh, fw);
   const bool geo_bad = mask && !geo_ok(B, D, H, W);          // only the LINEAR kernels decode voxel indices by reciprocal multiply
   hipStream_t st = (hipStream_t)stream;
   AM_HIP(hipMemsetAsync(sums, 0, sizeof(double) * 2 * C * NREP, st));
   RowGeo rg;
   if (mask && mkrows(rg, dtype, true, B, D, H, W, C, bshift, active_list, n_active)) {
-    DISPATCH_T(dtype, AM_LAUNCH(chan_stats_rows_kernel<float>, dim3(rows_blocks(rg)), dim3(rows_threads(rg)), 0, st, (const float*)x, rg, sums),
-               AM_LAUNCH(chan_stats_rows_kernel<bf16_t>, dim3(rows_blocks(rg)), dim3(rows_threads(rg)), 0, st, (const bf16_t*)x, rg, sums));
+    am_by_dtype(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      AM_LAUNCH(chan_stats_rows_kernel<T>, dim3(rows_blocks(rg)), dim3(rows_threads(rg)), 0, st, (const T*)x, rg, sums);
+    });
     AM_CHECK_LAUNCH();
     return 0;
   }
   if (geo_bad) return -4;
   const int nb = nblk((long)B * D * H * W, g.vpw);
-  DISPATCH_T(dtype, AM_LAUNCH_F32W(C, chan_stats_kernel, dim3(nb), st, (const float*)x, g, sums),
-             AM_LAUNCH(chan_stats_kernel<bf16_t>, dim3(nb), dim3(256), 0, st, (const bf16_t*)x, g, sums));
+  am_by_walk(dtype, C, [&](auto t, auto nt) {
+    using T = typename decltype(t)::type;
+    AM_LAUNCH((chan_stats_kernel<T, nt>), dim3(nb), dim3(nt), 0, st, (const T*)x, g, sums);
+  });
   AM_CHECK_LAUNCH();
   return 0;
 }
@@ -1856,39 +1844,30 @@ int am_norm_apply(int dtype, const void* x, int B, int D, int H, int W, int C, c
                   int fw, const float* scale, const float* shift, int act, const void* res, const float* stem_x,
                   const float* stem_w, const float* stem_b, const float* fill, void* y, const int32_t* active_list, int n_active,
                   void* stream) {
-  CHK_C(C);
+  if (!am_row_ok(dtype, C, F32_MAX_C_512)) return -1;
   Geo g = mkgeo(dtype, false, B, D, H, W, C, mask, bshift, fd, fh, fw);
   const bool geo_bad = mask && !geo_ok(B, D, H, W);          // only the LINEAR kernels decode voxel indices by reciprocal multiply
   hipStream_t st = (hipStream_t)stream;
   RowGeo rg;
   if (mask && !fill && !(res && stem_x) && mkrows(rg, dtype, false, B, D, H, W, C, bshift, active_list, n_active)) {
     const dim3 gr(rows_blocks(rg)), bl(rows_threads(rg));
-    const int mode = res ? 1 : (stem_x ? 2 : 0);
-#define AM_ROWS_APPLY(TT_, ACT_, MODE_)                                                                                        \
-    AM_LAUNCH((norm_apply_rows_kernel<TT_, ACT_, MODE_>), gr, bl, 0, st, (const TT_*)x, rg, scale, shift, (const TT_*)res, stem_x, stem_w, stem_b, (TT_*)y)
-#define AM_ROWS_APPLY_M(TT_, ACT_)                                                                                             \
-    do { if (mode == 0) AM_ROWS_APPLY(TT_, ACT_, 0); else if (mode == 1) AM_ROWS_APPLY(TT_, ACT_, 1); else AM_ROWS_APPLY(TT_, ACT_, 2); } while (0)
-#define AM_ROWS_APPLY_A(TT_)                                                                                                   \
-    do { if (act == AM_ACT_LRELU) AM_ROWS_APPLY_M(TT_, AM_ACT_LRELU); else if (act == AM_ACT_RELU6) AM_ROWS_APPLY_M(TT_, AM_ACT_RELU6); \
-         else AM_ROWS_APPLY_M(TT_, AM_ACT_NONE); } while (0)
-    DISPATCH_T(dtype, AM_ROWS_APPLY_A(float), AM_ROWS_APPLY_A(bf16_t));
-#undef AM_ROWS_APPLY_A
-#undef AM_ROWS_APPLY_M
-#undef AM_ROWS_APPLY
+    // compile-time activation (any other code: none, as ever) and mode: 0 plain, 1 + residual tensor, 2 + Cin=1 stem shortcut
+    const int racts = act == AM_ACT_LRELU || act == AM_ACT_RELU6 ? act : AM_ACT_NONE;
+    am_by_dtype_int<AM_ACT_NONE, AM_ACT_LRELU, AM_ACT_RELU6>(dtype, racts, [&](auto t, auto a) {
+      using T = typename decltype(t)::type;
+      am_by_int<0, 1, 2>(res ? 1 : (stem_x ? 2 : 0), [&](auto m) {
+        AM_LAUNCH((norm_apply_rows_kernel<T, a, m>), gr, bl, 0, st, (const T*)x, rg, scale, shift, (const T*)res, stem_x, stem_w, stem_b, (T*)y);
+      });
+    });
     AM_CHECK_LAUNCH();
     return 0;
   }
   if (geo_bad) return -4;
   const int nb = nblk((long)B * D * H * W, g.vpw);
-#define AM_NA_(A_, O_) do {                                                                                                             \
-    if (dtype == AM_DT_BF16) AM_LAUNCH((norm_apply_kernel<bf16_t, 256, A_>), dim3(nb), dim3(256), 0, st, (const bf16_t*)x, g, scale, shift, act, \
-                                (const bf16_t*)res, stem_x, stem_w, stem_b, fill, (bf16_t*)y);                                           \
-    else if (C / 4 > 256) AM_LAUNCH((norm_apply_kernel<float, 512>), dim3(nb), dim3(512), 0, st, (const float*)x, g, scale, shift, act,   \
-                                (const float*)res, stem_x, stem_w, stem_b, fill, (float*)y);                                             \
-    else AM_LAUNCH((norm_apply_kernel<float, 256, A_>), dim3(nb), dim3(256), 0, st, (const float*)x, g, scale, shift, act,                \
-                                (const float*)res, stem_x, stem_w, stem_b, fill, (float*)y); } while (0)
-  AM_BWD_SPEC(act, false, AM_NA_);
-#undef AM_NA_
+  am_by_walk_act(dtype, C, act, false, [&](auto t, auto nt, auto a, auto) {
+    using T = typename decltype(t)::type;
+    AM_LAUNCH((norm_apply_kernel<T, nt, a>), dim3(nb), dim3(nt), 0, st, (const T*)x, g, scale, shift, act, (const T*)res, stem_x, stem_w, stem_b, fill, (T*)y);
+  });
   AM_CHECK_LAUNCH();
   return 0;
 }
@@ -1898,7 +1877,7 @@ int am_norm_bwd_reduce(int dtype, const void* dout, const void* out, const void*
                        int fill, double* bsum, const float* pre_scale, const float* pre_shift, const int32_t* active_list,
                        int n_active, const double* count_ptr, double count_host, const float* gamma, float* k0, float* k1, float* k2,
                        float* dgamma, float* dbeta, float* dtoken, float* dbeta2, void* stream) {
-  CHK_C(C);
+  if (!am_row_ok(dtype, C, F32_MAX_C_512)) return -1;
   if (!out && act != AM_ACT_NONE && (!pre_scale || !pre_shift)) return -1;
   Geo g = mkgeo(dtype, true, B, D, H, W, C, mask, bshift, fd, fh, fw);
   const bool geo_bad = mask && !geo_ok(B, D, H, W);          // only the LINEAR kernels decode voxel indices by reciprocal multiply
@@ -1914,28 +1893,23 @@ int am_norm_bwd_reduce(int dtype, const void* dout, const void* out, const void*
   }
   RowGeo rg;
   if (mask && !fill && mkrows(rg, dtype, true, B, D, H, W, C, bshift, active_list, n_active)) {
-#define AM_RR_(A_, O_)                                                                                                                  \
-    DISPATCH_T(dtype,                                                                                                                    \
-               AM_LAUNCH((norm_bwd_reduce_rows_kernel<float, A_, O_>), dim3(rows_blocks(rg)), dim3(rows_threads(rg)), 0, st, (const float*)dout, \
-                         (const float*)out, (const float*)x, rg, mean, rstd, act, bsum, pre_scale, pre_shift, fin),                     \
-               AM_LAUNCH((norm_bwd_reduce_rows_kernel<bf16_t, A_, O_>), dim3(rows_blocks(rg)), dim3(rows_threads(rg)), 0, st, (const bf16_t*)dout, \
-                         (const bf16_t*)out, (const bf16_t*)x, rg, mean, rstd, act, bsum, pre_scale, pre_shift, fin))
-    AM_BWD_SPEC(act, out != nullptr, AM_RR_);
-#undef AM_RR_
+    am_by_dtype(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      am_by_act(act, out != nullptr, [&](auto a, auto o) {
+        AM_LAUNCH((norm_bwd_reduce_rows_kernel<T, a, o>), dim3(rows_blocks(rg)), dim3(rows_threads(rg)), 0, st, (const T*)dout, (const T*)out, (const T*)x, rg,
+                  mean, rstd, act, bsum, pre_scale, pre_shift, fin);
+      });
+    });
     AM_CHECK_LAUNCH();
     return 0;
   }
   if (geo_bad) return -4;
   const int nb = nblk((long)B * D * H * W, g.vpw);
-#define AM_RL_(A_, O_) do {                                                                                                             \
-    if (dtype == AM_DT_BF16) AM_LAUNCH((norm_bwd_reduce_kernel<bf16_t, 256, A_, O_>), dim3(nb), dim3(256), 0, st, (const bf16_t*)dout,   \
-                                (const bf16_t*)out, (const bf16_t*)x, g, mean, rstd, act, fill, bsum, pre_scale, pre_shift, fin);       \
-    else if (C / 4 > 256) AM_LAUNCH((norm_bwd_reduce_kernel<float, 512>), dim3(nb), dim3(512), 0, st, (const float*)dout,                \
-                                (const float*)out, (const float*)x, g, mean, rstd, act, fill, bsum, pre_scale, pre_shift, fin);         \
-    else AM_LAUNCH((norm_bwd_reduce_kernel<float, 256, A_, O_>), dim3(nb), dim3(256), 0, st, (const float*)dout,                         \
-                                (const float*)out, (const float*)x, g, mean, rstd, act, fill, bsum, pre_scale, pre_shift, fin); } while (0)
-  AM_BWD_SPEC(act, out != nullptr, AM_RL_);
-#undef AM_RL_
+  am_by_walk_act(dtype, C, act, out != nullptr, [&](auto t, auto nt, auto a, auto o) {
+    using T = typename decltype(t)::type;
+    AM_LAUNCH((norm_bwd_reduce_kernel<T, nt, a, o>), dim3(nb), dim3(nt), 0, st, (const T*)dout, (const T*)out, (const T*)x, g, mean, rstd, act, fill, bsum,
+              pre_scale, pre_shift, fin);
+  });
   AM_CHECK_LAUNCH();
   return 0;
 }
@@ -1954,7 +1928,7 @@ int am_norm_bwd_apply(int dtype, const void* dout, const void* out, const void* 
                       const float* k0, const float* k1, const float* k2, int act, void* dx, void* dres, float* dxsum_accum,
                       double* dxsum_scratch, const float* pre_scale, const float* pre_shift, const int32_t* active_list, int n_active,
                       int scratch_is_zero_workspace, void* stream) {
-  CHK_C(C);
+  if (!am_row_ok(dtype, C, F32_MAX_C_512)) return -1;
   if (!out && act != AM_ACT_NONE && (!pre_scale || !pre_shift)) return -1;
   Geo g = mkgeo(dtype, false, B, D, H, W, C, mask, bshift, fd, fh, fw);
   const bool geo_bad = mask && !geo_ok(B, D, H, W);          // only the LINEAR kernels decode voxel indices by reciprocal multiply
@@ -1976,24 +1950,19 @@ int am_norm_bwd_apply(int dtype, const void* dout, const void* out, const void* 
   unsigned* dx_ticket = fused ? (unsigned*)(dxsum_scratch + (size_t)AM_DXREP * C) : nullptr;
   if (rep && !fused) AM_HIP(hipMemsetAsync(dxsum_scratch, 0, sizeof(double) * AM_DXREP * C, st));
   if (rows) {
-#define AM_AR_(A_, O_)                                                                                                                  \
-    DISPATCH_T(dtype,                                                                                                                    \
-               AM_LAUNCH((norm_bwd_apply_rows_kernel<float, A_, O_>), dim3(nb), dim3(rows_threads(rg)), 0, st, (const float*)dout, (const float*)out, \
-                         (const float*)x, rg, mean, rstd, k0, k1, k2, act, (float*)dx, (float*)dres, dxs, nrep, pre_scale, pre_shift, dx_accum, dx_ticket), \
-               AM_LAUNCH((norm_bwd_apply_rows_kernel<bf16_t, A_, O_>), dim3(nb), dim3(rows_threads(rg)), 0, st, (const bf16_t*)dout, (const bf16_t*)out, \
-                         (const bf16_t*)x, rg, mean, rstd, k0, k1, k2, act, (bf16_t*)dx, (bf16_t*)dres, dxs, nrep, pre_scale, pre_shift, dx_accum, dx_ticket))
-    AM_BWD_SPEC(act, out != nullptr, AM_AR_);
-#undef AM_AR_
+    am_by_dtype(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      am_by_act(act, out != nullptr, [&](auto a, auto o) {
+        AM_LAUNCH((norm_bwd_apply_rows_kernel<T, a, o>), dim3(nb), dim3(rows_threads(rg)), 0, st, (const T*)dout, (const T*)out, (const T*)x, rg, mean, rstd,
+                  k0, k1, k2, act, (T*)dx, (T*)dres, dxs, nrep, pre_scale, pre_shift, dx_accum, dx_ticket);
+      });
+    });
   } else {
-#define AM_AL_(A_, O_) do {                                                                                                             \
-    if (dtype == AM_DT_BF16) AM_LAUNCH((norm_bwd_apply_kernel<bf16_t, 256, A_, O_>), dim3(nb), dim3(256), 0, st, (const bf16_t*)dout, (const bf16_t*)out, \
-                                (const bf16_t*)x, g, mean, rstd, k0, k1, k2, act, (bf16_t*)dx, (bf16_t*)dres, dxs, nrep, pre_scale, pre_shift, dx_accum, dx_ticket); \
-    else if (C / 4 > 256) AM_LAUNCH((norm_bwd_apply_kernel<float, 512>), dim3(nb), dim3(512), 0, st, (const float*)dout, (const float*)out, \
-                                (const float*)x, g, mean, rstd, k0, k1, k2, act, (float*)dx, (float*)dres, dxs, nrep, pre_scale, pre_shift, dx_accum, dx_ticket); \
-    else AM_LAUNCH((norm_bwd_apply_kernel<float, 256, A_, O_>), dim3(nb), dim3(256), 0, st, (const float*)dout, (const float*)out,        \
-                                (const float*)x, g, mean, rstd, k0, k1, k2, act, (float*)dx, (float*)dres, dxs, nrep, pre_scale, pre_shift, dx_accum, dx_ticket); } while (0)
-    AM_BWD_SPEC(act, out != nullptr, AM_AL_);
-#undef AM_AL_
+    am_by_walk_act(dtype, C, act, out != nullptr, [&](auto t, auto nt, auto a, auto o) {
+      using T = typename decltype(t)::type;
+      AM_LAUNCH((norm_bwd_apply_kernel<T, nt, a, o>), dim3(nb), dim3(nt), 0, st, (const T*)dout, (const T*)out, (const T*)x, g, mean, rstd,
+                k0, k1, k2, act, (T*)dx, (T*)dres, dxs, nrep, pre_scale, pre_shift, dx_accum, dx_ticket);
+    });
   }
   AM_CHECK_LAUNCH();
   if (rep && !fused) { AM_LAUNCH(rep_reduce_kernel, dim3((C + 255) / 256), dim3(256), 0, st, dxsum_scratch, AM_DXREP, C, dxsum_accum); AM_CHECK_LAUNCH(); }
@@ -2002,7 +1971,7 @@ int am_norm_bwd_apply(int dtype, const void* dout, const void* out, const void* 
 
 int am_chan_sum(int dtype, const void* x, int B, int D, int H, int W, int C, const uint8_t* mask, int bshift, int fd, int fh,
                 int fw, float* out_accum, void* stream) {
-  CHK_C(C);
+  if (!am_row_ok(dtype, C, F32_MAX_C_512)) return -1;
   Geo g = mkgeo(dtype, true, B, D, H, W, C, mask, bshift, fd, fh, fw);
   if (mask && !geo_ok(B, D, H, W)) return -4;
   hipStream_t st = (hipStream_t)stream;
@@ -2010,8 +1979,10 @@ int am_chan_sum(int dtype, const void* x, int B, int D, int H, int W, int C, con
   // (with several workgroups the per-workgroup sums arrive as fp32 atomics in any order)
   if ((long)B * D * H * W * C <= (4L << 20)) { g.vpw = (int)((long)B * D * H * W); const int vpp = walk_threads(C, dtype) / (C / (dtype == AM_DT_BF16 ? 8 : 4)) > 0 ? walk_threads(C, dtype) / (C / (dtype == AM_DT_BF16 ? 8 : 4)) : 1; g.vpw = (g.vpw + vpp - 1) / vpp * vpp; }
   const int nb = nblk((long)B * D * H * W, g.vpw);
-  DISPATCH_T(dtype, AM_LAUNCH_F32W(C, chan_sum_kernel, dim3(nb), st, (const float*)x, g, out_accum),
-             AM_LAUNCH(chan_sum_kernel<bf16_t>, dim3(nb), dim3(256), 0, st, (const bf16_t*)x, g, out_accum));
+  am_by_walk(dtype, C, [&](auto t, auto nt) {
+    using T = typename decltype(t)::type;
+    AM_LAUNCH((chan_sum_kernel<T, nt>), dim3(nb), dim3(nt), 0, st, (const T*)x, g, out_accum);
+  });
   AM_CHECK_LAUNCH();
   return 0;
 }
@@ -2020,8 +1991,10 @@ int am_add(int dtype, const void* a, const void* b, void* y, long n_elems, void*
   hipStream_t st = (hipStream_t)stream;
   const size_t nchunk = (size_t)n_elems / (dtype == AM_DT_BF16 ? 8 : 4);
   int nb = (int)((nchunk + 255) / 256); if (nb > 4096) nb = 4096; if (nb < 1) nb = 1;
-  DISPATCH_T(dtype, AM_LAUNCH(add_kernel<float>, dim3(nb), dim3(256), 0, st, (const float*)a, (const float*)b, (float*)y, nchunk),
-             AM_LAUNCH(add_kernel<bf16_t>, dim3(nb), dim3(256), 0, st, (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)y, nchunk));
+  am_by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    AM_LAUNCH(add_kernel<T>, dim3(nb), dim3(256), 0, st, (const T*)a, (const T*)b, (T*)y, nchunk);
+  });
   AM_CHECK_LAUNCH();
   return 0;
 }
@@ -2029,7 +2002,7 @@ int am_add(int dtype, const void* a, const void* b, void* y, long n_elems, void*
 int am_stem_conv_fwd(int dtype, const float* x, int B, int D, int H, int W, int C, int ksize, const uint8_t* mask, int bshift,
                      int fd, int fh, int fw, const float* w, const float* bias, void* y, float* partials,
                      const int32_t* active_list, int n_active, int* partial_rows_written, void* stream) {
-  CHK_C_NARROW(C);
+  if (!am_row_ok(dtype, C, F32_MAX_C_256)) return -1;
   if (ksize != 1 && ksize != 3) return -2;
   Geo g = mkgeo(dtype, false, B, D, H, W, C, mask, bshift, fd, fh, fw);
   hipStream_t st = (hipStream_t)stream;
@@ -2038,9 +2011,9 @@ int am_stem_conv_fwd(int dtype, const float* x, int B, int D, int H, int W, int 
   if (partial_rows_written) *partial_rows_written = B * (D / SBD) * (H / SBH) * (W / SBW);
   if (dtype == AM_DT_BF16 && ksize == 3 && active_list && n_active > 0 && (C == 32 || C == 64 || C == 96) && B <= 255 && fd <= 255 && fh <= 255 && fw <= 255) {
     const MaskView mv{mask, fd, fh, fw, bshift};
-    if (C == 32) AM_LAUNCH(stem_conv_mfma_kernel<2>, dim3(n_active), dim3(256), 0, st, x, D, H, W, C, mv, active_list, w, bias, (bf16_t*)y, partials);
-    else if (C == 64) AM_LAUNCH(stem_conv_mfma_kernel<4>, dim3(n_active), dim3(256), 0, st, x, D, H, W, C, mv, active_list, w, bias, (bf16_t*)y, partials);
-    else AM_LAUNCH(stem_conv_mfma_kernel<6>, dim3(n_active), dim3(256), 0, st, x, D, H, W, C, mv, active_list, w, bias, (bf16_t*)y, partials);
+    am_by_int<2, 4, 6>(C / 16, [&](auto ns) {                  // 16-channel MFMA tiles
+      AM_LAUNCH(stem_conv_mfma_kernel<ns>, dim3(n_active), dim3(256), 0, st, x, D, H, W, C, mv, active_list, w, bias, (bf16_t*)y, partials);
+    });
     AM_CHECK_LAUNCH();
     if (partial_rows_written) *partial_rows_written = n_active;
     return 0;
@@ -2052,13 +2025,10 @@ int am_stem_conv_fwd(int dtype, const float* x, int B, int D, int H, int W, int 
   size_t fl = (size_t)C * ksize * ksize * ksize;
   if (partials && fl < (size_t)256 * 8 * 2) fl = (size_t)256 * 8 * 2;    // the statistics fold reuses the weight area
   const size_t sm = sizeof(float) * (fl + (size_t)(SBD + 2 * pad_) * (SBH + 2 * pad_) * (SBW + 2 * pad_));
-  if (ksize == 3) {
-    DISPATCH_T(dtype, AM_LAUNCH((stem_conv_fwd_kernel<float, 3>), dim3(nb), dim3(256), sm, st, x, g, w, bias, (float*)y, partials),
-               AM_LAUNCH((stem_conv_fwd_kernel<bf16_t, 3>), dim3(nb), dim3(256), sm, st, x, g, w, bias, (bf16_t*)y, partials));
-  } else {
-    DISPATCH_T(dtype, AM_LAUNCH((stem_conv_fwd_kernel<float, 1>), dim3(nb), dim3(256), sm, st, x, g, w, bias, (float*)y, partials),
-               AM_LAUNCH((stem_conv_fwd_kernel<bf16_t, 1>), dim3(nb), dim3(256), sm, st, x, g, w, bias, (bf16_t*)y, partials));
-  }
+  am_by_dtype_int<1, 3>(dtype, ksize, [&](auto t, auto k) {
+    using T = typename decltype(t)::type;
+    AM_LAUNCH((stem_conv_fwd_kernel<T, k>), dim3(nb), dim3(256), sm, st, x, g, w, bias, (T*)y, partials);
+  });
   AM_CHECK_LAUNCH();
   return 0;
 }
@@ -2066,7 +2036,7 @@ int am_stem_conv_fwd(int dtype, const float* x, int B, int D, int H, int W, int 
 int am_stem_conv_wgrad(int dtype, const float* x, const void* dy, int B, int D, int H, int W, int C, int ksize,
                        const uint8_t* mask, int bshift, int fd, int fh, int fw, float* dw_accum, float* db_accum,
                        const int32_t* active_list, int n_active, float* det_workspace, long det_workspace_floats, void* stream) {
-  CHK_C_NARROW(C);
+  if (!am_row_ok(dtype, C, F32_MAX_C_256)) return -1;
   if (ksize != 1 && ksize != 3) return -2;
   Geo g = mkgeo(dtype, true, B, D, H, W, C, mask, bshift, fd, fh, fw);
   hipStream_t st = (hipStream_t)stream;
@@ -2080,16 +2050,15 @@ int am_stem_conv_wgrad(int dtype, const float* x, const void* dy, int B, int D, 
         if (nwg > det_workspace_floats / det_row) nwg = (int)(det_workspace_floats / det_row);
     }
     const size_t sm = (size_t)(18 * 18 * 18 + 8) * 4 + (size_t)256 * (2 * C + 32);
-#define AM_STEM_WG(NS_, K_)                                                                                                           \
-    {                                                                                                                                 \
-      auto kern = stem_wgrad_mfma_kernel<NS_, K_>;                                                                                    \
-      static PerDeviceOnce cap;                                                                                                       \
-      cap.run([&](int) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); (void)hipGetLastError(); }); \
-      AM_LAUNCH(kern, dim3(nwg), dim3(256), sm, st, x, (const bf16_t*)dy, D, H, W, mv, active_list, n_active, dw_accum, db_accum, det_workspace);     \
-    }
-    if (ksize == 3) { if (C == 32) AM_STEM_WG(2, 3) else if (C == 64) AM_STEM_WG(4, 3) else AM_STEM_WG(6, 3) }
-    else { if (C == 32) AM_STEM_WG(2, 1) else if (C == 64) AM_STEM_WG(4, 1) else AM_STEM_WG(6, 1) }
-#undef AM_STEM_WG
+    hipError_t optin = hipSuccess;
+    am_by_int<2, 4, 6>(C / 16, [&](auto ns) {
+      am_by_int<1, 3>(ksize, [&](auto k) {
+        constexpr auto kern = stem_wgrad_mfma_kernel<ns, k>;
+        if ((optin = am_lds_optin<kern>()) != hipSuccess) return;
+        AM_LAUNCH(kern, dim3(nwg), dim3(256), sm, st, x, (const bf16_t*)dy, D, H, W, mv, active_list, n_active, dw_accum, db_accum, det_workspace);
+      });
+    });
+    AM_HIP(optin);
     AM_CHECK_LAUNCH();
     if (det_workspace) {
       AM_LAUNCH(stem_wgrad_fold_kernel, dim3((unsigned)((det_row + 255) / 256)), dim3(256), 0, st, det_workspace, nwg, C, ksize * ksize * ksize, dw_accum, db_accum);
@@ -2103,21 +2072,24 @@ int am_stem_conv_wgrad(int dtype, const float* x, const void* dy, int B, int D, 
   if (nb > 1024) nb = 1024;                                   // persistent workgroups: one atomic flush each
   const int pad_ = ksize / 2;
   const size_t sm = sizeof(float) * ((size_t)C * (ksize * ksize * ksize + 1) + (size_t)(SBD + 2 * pad_) * (SBH + 2 * pad_) * (SBW + 2 * pad_));
-  DISPATCH_T(dtype,
-             AM_LAUNCH(stem_conv_wgrad_kernel<float>, dim3(nb), dim3(256), sm, st, x, (const float*)dy, g, ksize, dw_accum, db_accum),
-             AM_LAUNCH(stem_conv_wgrad_kernel<bf16_t>, dim3(nb), dim3(256), sm, st, x, (const bf16_t*)dy, g, ksize, dw_accum, db_accum));
+  am_by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    AM_LAUNCH(stem_conv_wgrad_kernel<T>, dim3(nb), dim3(256), sm, st, x, (const T*)dy, g, ksize, dw_accum, db_accum);
+  });
   AM_CHECK_LAUNCH();
   return 0;
 }
 
 int am_proj_fwd(int dtype, const void* x, long nvox, int C, const float* w, const float* b, const float* pre_scale, const float* pre_shift,
                 float* rec, void* stream) {
-  CHK_C_NARROW(C);
+  if (!am_row_ok(dtype, C, F32_MAX_C_256)) return -1;
   if ((pre_scale == nullptr) != (pre_shift == nullptr)) return -1;
   hipStream_t st = (hipStream_t)stream;
   const int nb = (int)((nvox + 255) / 256);
-  DISPATCH_T(dtype, AM_LAUNCH(proj_fwd_kernel<float>, dim3(nb), dim3(256), 0, st, (const float*)x, nvox, C, w, b, pre_scale, pre_shift, rec),
-             AM_LAUNCH(proj_fwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, st, (const bf16_t*)x, nvox, C, w, b, pre_scale, pre_shift, rec));
+  am_by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    AM_LAUNCH(proj_fwd_kernel<T>, dim3(nb), dim3(256), 0, st, (const T*)x, nvox, C, w, b, pre_scale, pre_shift, rec);
+  });
   AM_CHECK_LAUNCH();
   return 0;
 }
@@ -2125,31 +2097,37 @@ int am_proj_fwd(int dtype, const void* x, long nvox, int C, const float* w, cons
 int am_proj_norm_bwd(int dtype, const void* x, const float* drec, long nvox, int C, const float* w, const float* gamma, const float* beta,
                      const float* mean, const float* rstd, const float* scale, double* workspace, float* coef, void* dx,
                      float* dgamma_accum, float* dbeta_accum, float* dw_accum, float* db_accum, void* stream) {
-  CHK_C_NARROW(C);
+  if (!am_row_ok(dtype, C, F32_MAX_C_256)) return -1;
   if (!x || !drec || !w || !gamma || !beta || !mean || !rstd || !scale || !workspace || !coef || !dx || !dgamma_accum || !dbeta_accum ||
       !dw_accum || !db_accum || nvox <= 0) return -1;
   hipStream_t st = (hipStream_t)stream;
   ProjNormFin fin{(unsigned*)(workspace + (size_t)NREP * (C + 1)), (double)nvox, gamma, beta, rstd, scale, w,
                   coef, coef + C, coef + 2 * C, dgamma_accum, dbeta_accum, dw_accum, db_accum};
   const int vr = pick_vpw(nvox, C, dtype, true), va = pick_vpw(nvox, C, dtype, false);
-  DISPATCH_T(dtype, AM_LAUNCH(proj_norm_bwd_reduce_kernel<float>, dim3(nblk(nvox, vr)), dim3(256), 0, st, (const float*)x, drec, nvox, C, vr, mean, workspace, fin),
-             AM_LAUNCH(proj_norm_bwd_reduce_kernel<bf16_t>, dim3(nblk(nvox, vr)), dim3(256), 0, st, (const bf16_t*)x, drec, nvox, C, vr, mean, workspace, fin));
+  am_by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    AM_LAUNCH(proj_norm_bwd_reduce_kernel<T>, dim3(nblk(nvox, vr)), dim3(256), 0, st, (const T*)x, drec, nvox, C, vr, mean, workspace, fin);
+  });
   AM_CHECK_LAUNCH();
-  DISPATCH_T(dtype, AM_LAUNCH(proj_norm_bwd_apply_kernel<float>, dim3(nblk(nvox, va)), dim3(256), 0, st, (const float*)x, drec, nvox, C, va, mean, rstd, coef, coef + C, coef + 2 * C, (float*)dx),
-             AM_LAUNCH(proj_norm_bwd_apply_kernel<bf16_t>, dim3(nblk(nvox, va)), dim3(256), 0, st, (const bf16_t*)x, drec, nvox, C, va, mean, rstd, coef, coef + C, coef + 2 * C, (bf16_t*)dx));
+  am_by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    AM_LAUNCH(proj_norm_bwd_apply_kernel<T>, dim3(nblk(nvox, va)), dim3(256), 0, st, (const T*)x, drec, nvox, C, va, mean, rstd, coef, coef + C, coef + 2 * C, (T*)dx);
+  });
   AM_CHECK_LAUNCH();
   return 0;
 }
 
 int am_proj_bwd(int dtype, const void* x, const float* drec, long nvox, int C, const float* w, void* dx, float* dw_accum,
                 float* db_accum, float* det_workspace, long det_workspace_floats, void* stream) {
-  CHK_C_NARROW(C);
+  if (!am_row_ok(dtype, C, F32_MAX_C_256)) return -1;
   hipStream_t st = (hipStream_t)stream;
   const int vpw = pick_vpw(nvox, C, dtype, true);
   const int nb = nblk(nvox, vpw);
   if (det_workspace && det_workspace_floats < (long)nb * (C + 1)) return -6;
-  DISPATCH_T(dtype, AM_LAUNCH(proj_bwd_kernel<float>, dim3(nb), dim3(256), 0, st, (const float*)x, drec, nvox, C, vpw, w, (float*)dx, dw_accum, db_accum, det_workspace),
-             AM_LAUNCH(proj_bwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, st, (const bf16_t*)x, drec, nvox, C, vpw, w, (bf16_t*)dx, dw_accum, db_accum, det_workspace));
+  am_by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    AM_LAUNCH(proj_bwd_kernel<T>, dim3(nb), dim3(256), 0, st, (const T*)x, drec, nvox, C, vpw, w, (T*)dx, dw_accum, db_accum, det_workspace);
+  });
   AM_CHECK_LAUNCH();
   if (det_workspace) {
     AM_LAUNCH(rows_fold_kernel, dim3((C + 1 + 255) / 256), dim3(256), 0, st, det_workspace, nb, C + 1, C, dw_accum, db_accum);
@@ -2217,12 +2195,11 @@ int am_pack_weight(int dtype, const float* src, void* dst, int R, int K, int tap
   if (Rp < R || Kp < K) return -1;
   dim3 grid(Rp, (Kp + 63) / 64);
   const size_t sm = sizeof(float) * 64 * taps;
-  if (dtype == AM_DT_F32S) {
-    if (Kp % 16) return -1;
-    AM_LAUNCH(pack_weight_kernel<f32s_t>, grid, dim3(256), sm, st, src, (f32s_t*)dst, R, K, taps, stride_r, stride_k, Rp, Kp);
-  } else
-  DISPATCH_T(dtype, AM_LAUNCH(pack_weight_kernel<float>, grid, dim3(256), sm, st, src, (float*)dst, R, K, taps, stride_r, stride_k, Rp, Kp),
-             AM_LAUNCH(pack_weight_kernel<bf16_t>, grid, dim3(256), sm, st, src, (bf16_t*)dst, R, K, taps, stride_r, stride_k, Rp, Kp));
+  if (dtype == AM_DT_F32S && Kp % 16) return -1;
+  by_pack_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    AM_LAUNCH(pack_weight_kernel<T>, grid, dim3(256), sm, st, src, (T*)dst, R, K, taps, stride_r, stride_k, Rp, Kp);
+  });
   AM_CHECK_LAUNCH();
   return 0;
 }
@@ -2230,10 +2207,7 @@ int am_pack_weight(int dtype, const float* src, void* dst, int R, int K, int tap
 int am_pack_weights_batched(int dtype, const am_pack_desc* descs, int ndesc, int total_blocks, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   if (ndesc <= 0 || total_blocks <= 0) return 0;
-  if (dtype == AM_DT_F32S) AM_LAUNCH(pack_weights_batched_kernel<f32s_t>, dim3(total_blocks), dim3(256), 0, st, descs, ndesc);
-  else
-  DISPATCH_T(dtype, AM_LAUNCH(pack_weights_batched_kernel<float>, dim3(total_blocks), dim3(256), 0, st, descs, ndesc),
-             AM_LAUNCH(pack_weights_batched_kernel<bf16_t>, dim3(total_blocks), dim3(256), 0, st, descs, ndesc));
+  by_pack_dtype(dtype, [&](auto t) { AM_LAUNCH(pack_weights_batched_kernel<typename decltype(t)::type>, dim3(total_blocks), dim3(256), 0, st, descs, ndesc); });
   AM_CHECK_LAUNCH();
   return 0;
 }

@@ -1431,6 +1431,59 @@ def test_conv_rw_k3_s2_level1(ops, case, sparse):
     assert (st_a.sums.cpu()[0] - ref).abs().max().item() <= 2e-5 * ref.abs().max().item()
 
 
+def test_conv_on_a_second_device(ops):
+    """One process, second device: the per-device host state (CU count -> conv_k3's grid and partial rows, the dynamic-LDS opt-in of
+    every kernel instantiation) must be that of the device that launches, not of device 0.  A K3_CASES shape on conv_k3_kernel with
+    statistics rows and the block-sparse shape of test_conv_rw_k3_s1_level0 on conv_rw_kernel, each against its test's reference
+    (F.conv3d, then the mask) and tolerance; the rows the conv_k3 launch reports == am_conv3d_partials_rows asked on that device
+    (for the resident-weight kernel that answer is an upper bound, as on device 0)."""
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs a second device")
+    import ctypes
+    from anatomask_amd import hip
+    dtype, dev = torch.bfloat16, "cuda:1"
+    cl = lambda t: t.permute(0, 2, 3, 4, 1).contiguous().to(device=dev, dtype=dtype)
+
+    def rows_of(B, S, cin, cout, sparse, bs, n_active):
+        n = ctypes.c_int(0)
+        hip.lib().conv3d_partials_rows(ops.CONV_FWD, hip.DT_BF16, 3, 1, B, *S, cin, cout, int(sparse), bs, n_active, ctypes.addressof(n))
+        return n.value
+
+    with torch.cuda.device(1):
+        # dense k3 s1 on the persistent kernel (K3_CASES[5])
+        cin, cout, S, B = 64, 32, (32, 32, 64), 2
+        x = q(rnd(B, cin, *S, seed=71), dtype)
+        w = q(rnd(cout, cin, 3, 3, 3, seed=72, scale=1.0 / np.sqrt(cin * 27)), dtype)
+        bias = rnd(cout, seed=73)
+        yr = F.conv3d(x, w, bias, padding=1)
+        assert hip.lib()._lib.am_conv3d_uses_k3(ops.CONV_FWD, hip.DT_BF16, 3, 1, B, *S, cin, *S, cout, 0, 0, 0, 1) == 1
+        y, part = ops.conv3d(ops.CONV_FWD, cl(x), ops.pack_weight(w.to(dev), dtype, False, False), bias.to(dev), S, 3, 1, want_partials=True)
+        assert y.device == torch.device(dev) and part.rows == rows_of(B, S, cin, cout, False, 0, 0)
+        assert part.rows == 8 * torch.cuda.get_device_properties(1).multi_processor_count      # (one workgroup per CU, a multiple of the one channel tile)
+        close(from_cl(y), yr, TOL[dtype], "conv_k3 fwd on device 1")
+        st_a, st_b = ops.NormStats(cout, dev), ops.NormStats(cout, dev)
+        part.reduce(sums=st_a.sums)
+        ops.chan_stats(y, None, 0, st_b)
+        ref = st_b.sums.cpu().sum(0)
+        assert (st_a.sums.cpu()[0] - ref).abs().max().item() <= 1e-5 * ref.abs().max().item()
+        # block-sparse k3 s1 on the resident-weight kernel (test_conv_rw_k3_s1_level0, case (32, 32))
+        cin, cout, B, f, bs = 32, 32, 2, (1, 2, 3), 4
+        so = tuple(v << bs for v in f)
+        mask = mk_mask(B, f, 3, seed=5)
+        mi = ops.MaskInfo.from_bool(mask, dev)
+        mo = O.upsample_mask(mask, so).float()
+        x = q(rnd(B, cin, *so, seed=41), dtype) * mo
+        w = q(rnd(cout, cin, 3, 3, 3, seed=42, scale=1.0 / np.sqrt(cin * 27)), dtype)
+        bias = rnd(cout, seed=43)
+        yr = F.conv3d(x, w, bias, padding=1) * mo
+        xd = cl(x)
+        xd = torch.where(cl(mo.expand_as(x)) > 0, xd, torch.full_like(xd, float("nan")))      # inactive voxels may hold anything
+        y, part = ops.conv3d(ops.CONV_FWD, xd, ops.pack_weight(w.to(dev), dtype, False, False), bias.to(dev), so, 3, 1,
+                             in_mask=mi, in_bshift=bs, out_mask=mi, out_bshift=bs, want_partials=True)
+        assert part.rows <= 256 and part.rows <= rows_of(B, so, cin, cout, True, bs, mi.active_list()[1])      # one row per persistent workgroup, within the bound
+        close(from_cl(y), yr, TOL[dtype], "rw conv fwd on device 1", mo)
+
+
 def test_row_walk_kernels_beyond_the_linear_decode_limit(ops):
     """B * D * H * W * max(D, H, W) >= 2^32 (batch 16 at 128^3): the linear kernels' reciprocal-multiply voxel decode stops being exact
     there and they refuse (-4), but the row-walk kernels (active-patch list) have no such limit -- the norm passes of a block-sparse
