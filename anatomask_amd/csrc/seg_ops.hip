@@ -6,6 +6,8 @@
 //   seg_head     1x1 conv C -> K: plain (class-major logits) or accumulate (sum of the un-flipped mirrors, Gaussian-weighted, into the
 //                whole-volume accumulator; tiles run in order on one stream, no atomics: bitwise reproducible)
 //   seg_finalize acc / wsum over the un-padded crop (+ argmax labels)
+//   seg_export   the same crop and division, then softmax / sigmoid probabilities and argmax / region labels in one pass
+//                (LabelManager.apply_inference_nonlin + convert_probabilities_to_segmentation, label_handling.py:128-175)
 // Mirror m of a set of allowed axes (bit a of `axes` = spatial axis a): bit j of m flips the j-th allowed axis (ascending).  M = 2^popcount.
 #include "common.h"
 #include "../../include/anatomask_hip.h"
@@ -174,6 +176,116 @@ __global__ __launch_bounds__(256) void seg_finalize_kernel(const float* __restri
   }
 }
 
+constexpr int EV = 64;                                    // voxels per workgroup of the export (one per lane, 4 waves split the classes)
+constexpr int EXPORT_LDS_K = 600;                         // softmax probabilities: the workgroup's K x EV logits stay in LDS up to this K
+
+struct ExportArgs {
+  const float* acc; const float* wsum; int K, Xp, Yp, Zp, c0, c1, c2, X, Y, Z;
+  int nonlin; const int32_t* order; float* probs; void* labels; int staged;
+};
+
+// One workgroup owns EV consecutive voxels of the crop (grid-stride over such slabs); wave kg owns the classes kg, kg + 4, ...; lane v the
+// voxel.  l_k = acc[k][q] / wsum[q] exactly as seg_finalize.
+//   softmax: per-thread (max, argmax) -> 4-way combine through LDS (the lowest index wins a tie) -> labels; probabilities:
+//     staged (K <= EXPORT_LDS_K): l_k were kept in LDS, e_k = expf(l_k - max) replaces them, S = sum of the 4 partial sums, p_k = e_k / S:
+//       every accumulator element is read once;
+//     otherwise the first pass keeps a running (max, sum) per thread (rescaled when the max grows), the partials are rescaled to the common
+//       max, and a second read of the accumulator writes expf(l_k - max) / S;
+//   sigmoid: p_k = 1 / (1 + expf(-l_k)); label = order[highest k with p_k > 0.5], 0 when there is none (the reference's in-order overwrite).
+template <typename L>
+__global__ __launch_bounds__(256) void seg_export_kernel(ExportArgs a) {
+  extern __shared__ float s_lds[];
+  float* red_f = s_lds;                                   // [4][EV]
+  int* red_i = (int*)(s_lds + 4 * EV);                    // [4][EV]
+  float* sl = s_lds + 8 * EV;                             // [K][EV], staged only
+  const int K = a.K;
+  const long n = (long)a.X * a.Y * a.Z;
+  const long plane = (long)a.Xp * a.Yp * a.Zp;
+  const long slabs = (n + EV - 1) / EV;
+  const int lane = threadIdx.x & (EV - 1), kg = threadIdx.x >> 6;
+  const bool staged = a.staged != 0;
+  L* labels = (L*)a.labels;
+  for (long t = blockIdx.x; t < slabs; t += gridDim.x) {
+    const long i = t * EV + lane;
+    const bool valid = i < n;
+    long q = 0;
+    float w = 1.f;
+    if (valid) {
+      long r = i;
+      const int z = (int)(r % a.Z); r /= a.Z;
+      const int y = (int)(r % a.Y);
+      const int x = (int)(r / a.Y);
+      q = ((long)(x + a.c0) * a.Yp + (y + a.c1)) * a.Zp + (z + a.c2);
+      w = a.wsum[q];
+    }
+    const float* ap = a.acc + q;
+    float* pp = a.probs + i;                              // (dereferenced only when a.probs and valid)
+    if (a.nonlin == AM_SEG_SIGMOID) {
+      int last = -1;
+      if (valid)
+        for (int k = kg; k < K; k += 4) {
+          const float p = 1.f / (1.f + expf(-(ap[(long)k * plane] / w)));
+          if (a.probs) pp[(long)k * n] = p;
+          if (p > 0.5f) last = k;
+        }
+      if (labels) {
+        red_i[kg * EV + lane] = last;
+        __syncthreads();
+        if (kg == 0 && valid) {
+          for (int j = 1; j < 4; ++j) last = max(last, red_i[j * EV + lane]);
+          labels[i] = last < 0 ? (L)0 : (L)a.order[last];
+        }
+        __syncthreads();
+      }
+      continue;
+    }
+    float m = -INFINITY, s = 0.f;
+    int arg = 0x7fffffff;
+    if (valid)
+      for (int k = kg; k < K; k += 4) {
+        const float l = ap[(long)k * plane] / w;
+        if (staged) sl[k * EV + lane] = l;
+        const bool up = k == kg || l > m;                 // strict >: the lowest index wins a tie (torch.argmax)
+        if (a.probs && !staged) s = up ? s * expf(m - l) + 1.f : s + expf(l - m);
+        if (up) { m = l; arg = k; }
+      }
+    red_f[kg * EV + lane] = m;
+    red_i[kg * EV + lane] = arg;
+    __syncthreads();
+    float mx = red_f[lane];
+    int am = red_i[lane];
+    for (int j = 1; j < 4; ++j) {
+      const float mj = red_f[j * EV + lane];
+      const int aj = red_i[j * EV + lane];
+      if (mj > mx || (mj == mx && aj < am)) { mx = mj; am = aj; }
+    }
+    if (labels && kg == 0 && valid) labels[i] = (L)am;
+    if (a.probs) {
+      float ps = 0.f;
+      if (staged) {
+        if (valid)
+          for (int k = kg; k < K; k += 4) {
+            const float e = expf(sl[k * EV + lane] - mx);
+            sl[k * EV + lane] = e;
+            ps += e;
+          }
+      } else if (s != 0.f) {
+        ps = s * expf(m - mx);
+      }
+      __syncthreads();                                    // every thread has read the (max, argmax) partials
+      red_f[kg * EV + lane] = ps;
+      __syncthreads();
+      const float S = ((red_f[lane] + red_f[EV + lane]) + red_f[2 * EV + lane]) + red_f[3 * EV + lane];
+      if (valid)
+        for (int k = kg; k < K; k += 4) {
+          const float e = staged ? sl[k * EV + lane] : expf(ap[(long)k * plane] / w - mx);
+          pp[(long)k * n] = e / S;
+        }
+    }
+    __syncthreads();                                      // the reduction rows are reused by the next slab
+  }
+}
+
 inline int grid_for(long n) {
   long nb = (n + 255) / 256;
   if (nb > 65536) nb = 65536;
@@ -259,6 +371,27 @@ int am_seg_finalize(const float* acc, const float* wsum, int K, int Xp, int Yp, 
   else
     AM_LAUNCH(seg_finalize_kernel<uint8_t>, dim3(grid_for(n)), dim3(256), 0, st, acc, wsum, K, Xp, Yp, Zp, c0, c1, c2, X, Y, Z, logits,
               (uint8_t*)labels);
+  AM_CHECK_LAUNCH();
+  return 0;
+}
+
+int am_seg_export(const float* acc, const float* wsum, int K, int Xp, int Yp, int Zp, int c0, int c1, int c2, int X, int Y, int Z, int nonlin,
+                  const int32_t* region_order, float* probs, void* labels, int label_bytes, void* stream) {
+  if (!acc || !wsum || K <= 0 || X <= 0 || Y <= 0 || Z <= 0 || c0 < 0 || c1 < 0 || c2 < 0) return -2;
+  if (c0 + X > Xp || c1 + Y > Yp || c2 + Z > Zp) return -2;
+  if (!probs && !labels) return -2;
+  if (nonlin == AM_SEG_SOFTMAX ? region_order != nullptr : (nonlin != AM_SEG_SIGMOID || !region_order)) return -2;
+  if (labels && label_bytes != 1 && label_bytes != 2) return -2;
+  if (labels && nonlin == AM_SEG_SOFTMAX && K - 1 > (label_bytes == 1 ? 255 : 32767)) return -2;
+  ExportArgs a{acc, wsum, K, Xp, Yp, Zp, c0, c1, c2, X, Y, Z, nonlin, region_order, probs, labels, 0};
+  a.staged = nonlin == AM_SEG_SOFTMAX && probs && K <= EXPORT_LDS_K;
+  const size_t lds = (size_t)(8 + (a.staged ? K : 0)) * EV * sizeof(float);
+  long slabs = ((long)X * Y * Z + EV - 1) / EV;
+  if (slabs > 65536) slabs = 65536;
+  hipStream_t st = (hipStream_t)stream;
+  AM_HIP((am_lds_optin<seg_export_kernel<uint8_t>, seg_export_kernel<int16_t>>()));
+  if (labels && label_bytes == 2) AM_LAUNCH(seg_export_kernel<int16_t>, dim3((unsigned)slabs), dim3(256), lds, st, a);
+  else AM_LAUNCH(seg_export_kernel<uint8_t>, dim3((unsigned)slabs), dim3(256), lds, st, a);
   AM_CHECK_LAUNCH();
   return 0;
 }

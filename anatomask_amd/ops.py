@@ -776,3 +776,43 @@ def seg_finalize(acc: torch.Tensor, wsum: torch.Tensor, crop_start, crop_size, w
     hip.lib().seg_finalize(acc.data_ptr(), wsum.data_ptr(), K, *acc.shape[1:], *(int(c) for c in crop_start), *(int(s) for s in crop_size),
                            _p(logits), _p(labels), labels.element_size() if labels is not None else 1, _stream())
     return logits, labels
+
+
+SEG_SOFTMAX, SEG_SIGMOID = 0, 1   # AM_SEG_SOFTMAX / AM_SEG_SIGMOID
+
+
+def seg_export(acc: torch.Tensor, wsum: torch.Tensor, crop_start, crop_size, nonlin: str = "softmax", regions_class_order=None,
+               want_probabilities: bool = True, want_labels: bool = True):
+    """(probabilities fp32 [K,X,Y,Z] or None, labels [X,Y,Z] or None) of acc / wsum over the crop in one pass.  nonlin "softmax": labels =
+    argmax of the logits (seg_finalize's labels); "sigmoid": labels = 0, then regions_class_order[i] wherever p_i > 0.5, in order.  Labels
+    are uint8 when the largest possible label (K - 1, or max(regions_class_order)) is <= 255, else int16."""
+    K = acc.shape[0]
+    if nonlin not in ("softmax", "sigmoid"):
+        raise ValueError(f"nonlin {nonlin!r}: 'softmax' or 'sigmoid'")
+    order = None
+    if nonlin == "softmax":
+        if regions_class_order is not None:
+            raise ValueError("regions_class_order belongs to nonlin='sigmoid' (region-based labels), not to softmax")
+        top = K - 1
+    else:
+        if regions_class_order is None:
+            raise ValueError("nonlin='sigmoid' needs regions_class_order")
+        order = [int(c) for c in regions_class_order]
+        if len(order) != K:
+            raise ValueError(f"regions_class_order has {len(order)} entries for {K} regions")
+        if any(c < 0 or c > 32767 for c in order):
+            raise ValueError(f"regions_class_order {order}: labels must lie in [0, 32767]")
+        top = max(order)
+    if top > 32767:
+        raise ValueError(f"label {top} does not fit int16")
+    if not (want_probabilities or want_labels):
+        raise ValueError("seg_export: nothing asked for (want_probabilities and want_labels are both False)")
+    assert acc.dtype == torch.float32 and wsum.dtype == torch.float32 and acc.is_contiguous() and wsum.is_contiguous()
+    assert tuple(acc.shape[1:]) == tuple(wsum.shape)
+    order_t = torch.tensor(order, dtype=torch.int32, device=acc.device) if order is not None else None
+    probs = torch.empty(K, *crop_size, device=acc.device, dtype=torch.float32) if want_probabilities else None
+    labels = torch.empty(*crop_size, device=acc.device, dtype=torch.uint8 if top <= 255 else torch.int16) if want_labels else None
+    hip.lib().seg_export(acc.data_ptr(), wsum.data_ptr(), K, *acc.shape[1:], *(int(c) for c in crop_start), *(int(s) for s in crop_size),
+                         SEG_SIGMOID if order is not None else SEG_SOFTMAX, _p(order_t), _p(probs), _p(labels),
+                         labels.element_size() if labels is not None else 1, _stream())
+    return probs, labels

@@ -2,11 +2,17 @@
 
     python -m anatomask_amd.predict CASE.npz|CASE.npy CHECKPOINT.pth OUT_PREFIX [--model B|L|H] [--num-classes K]
            [--patch-size 128 128 128] [--dtype bf16|f32] [--step 0.5] [--no-mirroring] [--no-gaussian] [--save-logits]
+           [--folds CKPT [CKPT ...]] [--save-probabilities] [--regions-class-order I [I ...]]
 
 CASE: `.npz` with key `data` or `.npy`, [C=1, X, Y, Z] (nnU-Net's preprocessed layout).  CHECKPOINT: a torch file with `network_weights`
-(an nnU-Net checkpoint) or a bare state dict.  Writes OUT_PREFIX_labels.npy (uint8 for K <= 255, else int16) and, with --save-logits,
-OUT_PREFIX_logits.npy (fp32 [K, X, Y, Z]).  Without --model the network's dims / depth / classes are read off the weights' shapes.
-The predictor is nnUNetPredictor(tile_step_size=0.5, use_gaussian=True, use_mirroring=True) of P/direct_infer.py by default."""
+(an nnU-Net checkpoint) or a bare state dict.  Writes OUT_PREFIX_labels.npy (uint8 when the largest label is <= 255, else int16) and, with
+--save-logits, OUT_PREFIX_logits.npy (fp32 [K, X, Y, Z]).  Without --model the network's dims / depth / classes are read off the weights'
+shapes.  The predictor is nnUNetPredictor(tile_step_size=0.5, use_gaussian=True, use_mirroring=True) of P/direct_infer.py by default.
+
+--folds names further checkpoints of the same architecture: the logits are the mean over CHECKPOINT and every fold
+(predict_logits_from_preprocessed_data), and everything written comes from that mean.  --save-probabilities writes OUT_PREFIX.npz with key
+`probabilities` (fp32 [K, X, Y, Z]; the file nnUNetv2_ensemble reads).  --regions-class-order selects region-based labels: sigmoid instead of
+softmax, labels = 0, then I_i wherever p_i > 0.5, in order (LabelManager.convert_probabilities_to_segmentation)."""
 from __future__ import annotations
 
 import argparse
@@ -16,7 +22,7 @@ import sys
 import numpy as np
 import torch
 
-from . import modules, segmentation
+from . import modules, ops, segmentation
 
 
 def load_case(path: str) -> np.ndarray:
@@ -48,7 +54,7 @@ def architecture_of(sd) -> dict:
     return dict(dims=dims, depth=depth, num_classes=int(sd["seg_outputs.4.weight"].shape[0]))
 
 
-def main(argv=None) -> int:
+def parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="python -m anatomask_amd.predict", description=__doc__.split("\n\n")[0])
     ap.add_argument("case")
     ap.add_argument("checkpoint")
@@ -61,8 +67,15 @@ def main(argv=None) -> int:
     ap.add_argument("--no-mirroring", action="store_true")
     ap.add_argument("--no-gaussian", action="store_true")
     ap.add_argument("--save-logits", action="store_true")
+    ap.add_argument("--folds", nargs="+", default=[], metavar="CKPT")
+    ap.add_argument("--save-probabilities", action="store_true")
+    ap.add_argument("--regions-class-order", type=int, nargs="+", default=None, metavar="I")
     ap.add_argument("--device", default="cuda:0")
-    a = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None) -> int:
+    a = parser().parse_args(argv)
 
     sd = load_weights(a.checkpoint)
     arch = architecture_of(sd)
@@ -72,6 +85,21 @@ def main(argv=None) -> int:
             raise SystemExit(f"--model {a.model} does not match the checkpoint (dims {arch['dims']}, depth {arch['depth']})")
     if a.num_classes is not None and a.num_classes != arch["num_classes"]:
         raise SystemExit(f"--num-classes {a.num_classes} does not match the checkpoint's heads ({arch['num_classes']})")
+    folds = [sd]
+    for path in a.folds:
+        fsd = load_weights(path)
+        try:
+            farch = architecture_of(fsd)
+        except (ValueError, KeyError) as e:
+            raise SystemExit(f"--folds {path}: {e}")
+        if farch != arch:
+            raise SystemExit(f"--folds {path} is another architecture ({farch}) than {a.checkpoint} ({arch})")
+        folds.append(fsd)
+    if a.regions_class_order is not None:
+        if len(a.regions_class_order) != arch["num_classes"]:
+            raise SystemExit(f"--regions-class-order has {len(a.regions_class_order)} entries for {arch['num_classes']} regions")
+        if any(c < 0 or c > 32767 for c in a.regions_class_order):
+            raise SystemExit(f"--regions-class-order {a.regions_class_order}: labels must lie in [0, 32767]")
     net = segmentation.STUNet(1, arch["num_classes"], depth=arch["depth"], dims=arch["dims"], enable_deep_supervision=False)
     net.load_state_dict(sd)
     net.compute_dtype = torch.bfloat16 if a.dtype == "bf16" else torch.float32
@@ -79,11 +107,23 @@ def main(argv=None) -> int:
     pred = segmentation.SlidingWindowPredictor(net, a.patch_size, tile_step_size=a.step, use_gaussian=not a.no_gaussian,
                                                use_mirroring=not a.no_mirroring)
     image = torch.from_numpy(np.ascontiguousarray(load_case(a.case), dtype=np.float32))
+    params = folds if a.folds else None
+    export = a.save_probabilities or a.regions_class_order is not None
+    logits = probs = None
     with torch.no_grad():
-        logits, labels = pred.predict_logits_and_labels(image) if a.save_logits else (None, pred.predict_labels(image))
+        acc, wsum, below, size = pred.accumulate(image, params)
+        if export:
+            probs, labels = ops.seg_export(acc, wsum, below, size, "sigmoid" if a.regions_class_order is not None else "softmax",
+                                           a.regions_class_order, a.save_probabilities, True)
+            if a.save_logits:
+                logits = ops.seg_finalize(acc, wsum, below, size, True, False)[0]
+        else:
+            logits, labels = ops.seg_finalize(acc, wsum, below, size, a.save_logits, True)
     np.save(a.out_prefix + "_labels.npy", labels.cpu().numpy())
     if a.save_logits:
         np.save(a.out_prefix + "_logits.npy", logits.cpu().numpy())
+    if a.save_probabilities:
+        np.savez_compressed(a.out_prefix + ".npz", probabilities=probs.cpu().numpy())
     print(f"{a.case}: {tuple(image.shape[1:])} -> {a.out_prefix}_labels.npy ({arch['num_classes']} classes)")
     return 0
 

@@ -214,7 +214,11 @@ class SlidingWindowPredictor:
             self._gauss[key] = compute_gaussian(self.patch_size).to(device).contiguous()
         return self._gauss[key]
 
-    def _run(self, image: torch.Tensor, want_logits: bool, want_labels: bool, timed: bool = False):
+    def accumulate(self, image: torch.Tensor, list_of_parameters=None, timed: bool = False):
+        """(acc, wsum, pad_below, size): every tile of the padded volume through the network and the accumulating head, once per state dict
+        of `list_of_parameters` (None: the weights the network holds) into ONE accumulator pair.  seg_head_accumulate adds the Gaussian to
+        wsum once per fold, so acc / wsum is the mean over the folds (predict_logits_from_preprocessed_data, predict_from_raw_data.py:562-620,
+        without its division).  The network keeps the last fold's weights, as there."""
         net = self.network
         net._check_inference()
         if not isinstance(image, torch.Tensor) or image.dim() != 4:
@@ -224,42 +228,51 @@ class SlidingWindowPredictor:
         dev = next(net.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("move the network to a cuda (ROCm) device first")
+        folds = [None] if list_of_parameters is None else list(list_of_parameters)
+        if not folds:
+            raise ValueError("list_of_parameters is empty")
         vol = image[0].to(device=dev, dtype=torch.float32).contiguous()
         size = tuple(vol.shape)
         below, padded = padding_for(size, self.patch_size)
         steps = compute_steps_for_sliding_window(padded, self.patch_size, self.tile_step_size)
         axes = ops.mirror_axes_mask(self.allowed_mirroring_axes) if self.use_mirroring else 0
-        W, pk = net._engine_ctx()
-        hw, hb = net._head(4)
-        K = hw.shape[0]
+        K = net.num_classes
         acc = torch.zeros(K, *padded, device=dev, dtype=torch.float32)
         wsum = torch.zeros(*padded, device=dev, dtype=torch.float32)
         g = self._gaussian(dev) if self.use_gaussian else None
         tiles = torch.empty(1 << bin(axes).count("1"), *self.patch_size, device=dev, dtype=torch.float32)
         t = {"gather": 0.0, "network": 0.0, "head": 0.0} if timed else None
         ev = (lambda: torch.cuda.Event(enable_timing=True)) if timed else None
-        for sx in steps[0]:
-            for sy in steps[1]:
-                for sz in steps[2]:
-                    if timed:
-                        e = [ev() for _ in range(4)]
-                        e[0].record()
-                    ops.seg_gather(vol, (sx - below[0], sy - below[1], sz - below[2]), self.patch_size, axes, out=tiles)
-                    if timed:
-                        e[1].record()
-                    f = net.features(tiles, W, pk)[0]
-                    if timed:
-                        e[2].record()
-                    ops.seg_head_accumulate(f, axes, hw, hb, g, acc, wsum, (sx, sy, sz))
-                    if timed:
-                        e[3].record()
-                        torch.cuda.synchronize(dev)
-                        t["gather"] += e[0].elapsed_time(e[1]) / 1e3
-                        t["network"] += e[1].elapsed_time(e[2]) / 1e3
-                        t["head"] += e[2].elapsed_time(e[3]) / 1e3
-        logits, labels = ops.seg_finalize(acc, wsum, below, size, want_logits, want_labels)
+        for params in folds:
+            if params is not None:
+                net.load_state_dict(params)
+            W, pk = net._engine_ctx()                  # re-fetched per fold: the packed copies and the head follow the new masters
+            hw, hb = net._head(4)
+            for sx in steps[0]:
+                for sy in steps[1]:
+                    for sz in steps[2]:
+                        if timed:
+                            e = [ev() for _ in range(4)]
+                            e[0].record()
+                        ops.seg_gather(vol, (sx - below[0], sy - below[1], sz - below[2]), self.patch_size, axes, out=tiles)
+                        if timed:
+                            e[1].record()
+                        f = net.features(tiles, W, pk)[0]
+                        if timed:
+                            e[2].record()
+                        ops.seg_head_accumulate(f, axes, hw, hb, g, acc, wsum, (sx, sy, sz))
+                        if timed:
+                            e[3].record()
+                            torch.cuda.synchronize(dev)
+                            t["gather"] += e[0].elapsed_time(e[1]) / 1e3
+                            t["network"] += e[1].elapsed_time(e[2]) / 1e3
+                            t["head"] += e[2].elapsed_time(e[3]) / 1e3
         self.phase_seconds = t
-        return logits, labels
+        return acc, wsum, below, size
+
+    def _run(self, image: torch.Tensor, want_logits: bool, want_labels: bool, timed: bool = False, list_of_parameters=None):
+        acc, wsum, below, size = self.accumulate(image, list_of_parameters, timed)
+        return ops.seg_finalize(acc, wsum, below, size, want_logits, want_labels)
 
     def predict_sliding_window_return_logits(self, image: torch.Tensor) -> torch.Tensor:
         """image [1, X, Y, Z] -> logits fp32 [K, X, Y, Z] on the network's device."""
@@ -271,3 +284,17 @@ class SlidingWindowPredictor:
 
     def predict_logits_and_labels(self, image: torch.Tensor):
         return self._run(image, True, True)
+
+    def predict_logits_from_preprocessed_data(self, image: torch.Tensor, list_of_parameters=None) -> torch.Tensor:
+        """predict_from_raw_data.py:562-620: the mean over the folds (state dicts with the network's keys and shapes; None = the weights
+        the network holds) of the sliding-window logits, fp32 [K, X, Y, Z].  Afterwards the network holds the last fold's weights."""
+        return self._run(image, True, False, list_of_parameters=list_of_parameters)[0]
+
+    def predict_probabilities_and_labels(self, image: torch.Tensor, list_of_parameters=None, regions_class_order=None,
+                                         want_probabilities: bool = True):
+        """(probabilities fp32 [K, X, Y, Z] or None, labels [X, Y, Z]) of the fold-mean logits, from the fused export kernel:
+        LabelManager.apply_inference_nonlin + convert_probabilities_to_segmentation (label_handling.py:128-175).  Softmax + argmax of the
+        logits, or, exactly when `regions_class_order` is given, sigmoid + the region rule."""
+        acc, wsum, below, size = self.accumulate(image, list_of_parameters)
+        return ops.seg_export(acc, wsum, below, size, "sigmoid" if regions_class_order is not None else "softmax", regions_class_order,
+                              want_probabilities, True)

@@ -410,6 +410,19 @@ int am_seg_head_accumulate(int dtype, const void* f, int axes, int T0, int T1, i
  * written) and / or labels [X][Y][Z] = argmax over k (the lowest index on ties, as torch.argmax; label_bytes 1: uint8, K <= 255; 2: int16). */
 int am_seg_finalize(const float* acc, const float* wsum, int K, int Xp, int Yp, int Zp, int c0, int c1, int c2, int X, int Y, int Z,
                     float* logits, void* labels, int label_bytes, void* stream);
+/* Fused export of the same crop: logit l_k = acc[k][q] / wsum[q] (bitwise am_seg_finalize's), then LabelManager.apply_inference_nonlin and
+ * convert_probabilities_to_segmentation (nnunetv2/utilities/label_handling/label_handling.py:128-175) without an intermediate K x voxels array:
+ *   AM_SEG_SOFTMAX: p_k = expf(l_k - max) / sum_j expf(l_j - max); labels = argmax of the LOGITS (lowest index on ties), so asking for
+ *                   probabilities never changes a label am_seg_finalize returns; region_order must be NULL.
+ *   AM_SEG_SIGMOID: p_k = 1 / (1 + expf(-l_k)); labels = 0, then for i = 0..K-1 in order: p_i > 0.5f -> region_order[i] (device int32 [K];
+ *                   the comparison is on the computed fp32 p_i, as the reference's).
+ * probs fp32 [K][X][Y][Z] and / or labels [X][Y][Z] (NULL: not written; both NULL: -2).  label_bytes 1: uint8, 2: int16; the caller guarantees
+ * that the largest label (K - 1, or max(region_order)) fits.  Any K: up to K = 600 the workgroup's logits stay in LDS and acc is read once,
+ * above that it is read twice. */
+#define AM_SEG_SOFTMAX 0
+#define AM_SEG_SIGMOID 1
+int am_seg_export(const float* acc, const float* wsum, int K, int Xp, int Yp, int Zp, int c0, int c1, int c2, int X, int Y, int Z, int nonlin,
+                  const int32_t* region_order, float* probs, void* labels, int label_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,12 +1,17 @@
 """Seconds per volume of STUNet sliding-window inference: this package's HIP path vs the same network as plain torch under
 torch.autocast fp16 with torch.flip mirroring (the reference predictor's configuration, predict_from_raw_data.py:595-754) on the same GPU.
 
-    python tools/seg_bench.py [--repeats 3] [--size 256] [--dtype bf16|f32] [--skip-torch]
+    python tools/seg_bench.py [--repeats 3] [--size 256] [--dtype bf16|f32] [--skip-torch] [--export]
 
 Workload: STUNet-B, 105 classes, patch 128^3, step 0.5, mirroring over (0, 1, 2), Gaussian on; a seeded synthetic 1 x 256^3 volume
 (27 tiles x 8 mirrors).  Host clock around device-synchronised work, one warm-up volume, median of --repeats.  The HIP path's phase
 split (gather / network / head + accumulate) comes from a separate timed volume (device events per phase, synchronised per tile).
-Prints one JSON line."""
+Prints one JSON line.
+
+--export adds a second JSON line: ops.seg_export (softmax probabilities + labels in one pass) at K = 105 on a --size^3 accumulator against
+the torch sequence it replaces on the same device (ops.seg_finalize logits, torch.softmax(dim=0), argmax(0)).  Device events around each
+call, one warm-up each, the two alternated, median of max(--repeats, 5).  Both are also given as a fraction of the traffic floor: K N 4
+bytes read + K N 4 written at the 8.0 TB/s HBM peak."""
 import argparse
 import json
 import os
@@ -100,12 +105,56 @@ def timed(fn, repeats):
     return statistics.median(ts), ts
 
 
+HBM_PEAK = 8.0e12      # bytes / s, MI355X specification
+
+
+def export_bench(size, repeats, dev):
+    from anatomask_amd import ops
+    K, n = 105, (size,) * 3
+    g = torch.Generator(device=dev).manual_seed(0)
+    acc = torch.empty(K, *n, device=dev)
+    for k in range(K):
+        acc[k] = 8 * torch.randn(*n, device=dev, generator=g)
+    wsum = torch.rand(*n, device=dev, generator=g) + 0.5
+
+    def fused():
+        return ops.seg_export(acc, wsum, (0, 0, 0), n)
+
+    def sequence():
+        logits = ops.seg_finalize(acc, wsum, (0, 0, 0), n, True, False)[0]
+        probs = torch.softmax(logits, dim=0)
+        return probs, probs.argmax(0)
+
+    def once(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        torch.cuda.synchronize()
+        del out
+        return e0.elapsed_time(e1) / 1e3
+
+    once(fused), once(sequence)
+    tf, ts = [], []
+    for _ in range(max(repeats, 5)):
+        tf.append(once(fused))
+        ts.append(once(sequence))
+    f, q = statistics.median(tf), statistics.median(ts)
+    floor_bytes = 2 * K * size ** 3 * 4
+    floor_s = floor_bytes / HBM_PEAK
+    return {"workload": f"export K={K} on {size}^3: softmax probabilities + labels", "floor_bytes": floor_bytes,
+            "floor_s_at_8TBps": round(floor_s, 6), "fused_s": round(f, 6), "fused_runs": [round(t, 6) for t in tf],
+            "fused_fraction_of_floor": round(floor_s / f, 4), "torch_sequence_s": round(q, 6), "torch_runs": [round(t, 6) for t in ts],
+            "torch_fraction_of_floor": round(floor_s / q, 4), "speedup": round(q / f, 3), "device": torch.cuda.get_device_name(0)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--dtype", choices=["bf16", "f32"], default="bf16")
     ap.add_argument("--skip-torch", action="store_true")
+    ap.add_argument("--export", action="store_true")
     a = ap.parse_args()
     dev = "cuda:0"
     cfg = modules.STUNET_CONFIGS["B"]
@@ -136,6 +185,10 @@ def main():
                     "speedup": round(t_s / hip_s, 3)})
     out["device"] = torch.cuda.get_device_name(0)
     print(json.dumps(out))
+    if a.export:
+        del pred, net
+        torch.cuda.empty_cache()
+        print(json.dumps(export_bench(a.size, a.repeats, dev)))
 
 
 if __name__ == "__main__":
