@@ -183,8 +183,8 @@ __device__ __forceinline__ int crow(int R) { return ((R >> 5) << 5) + (((R >> 2)
 // launch with a clean error slate: hipGetLastError() is per-thread sticky and torch's own probing calls
 // can leave a benign error behind that would otherwise be mis-attributed to our launch
 #define AM_LAUNCH(...) do { (void)hipGetLastError(); hipLaunchKernelGGL(__VA_ARGS__); } while (0)
-// The kernel-selection stages (conv_rw / conv_gather / conv_k3 / conv_k3t / conv_wgk3 _launch) answer 1 = served, 0 = the shape does not
-// qualify.  hipErrorInvalidValue IS 1 (what a rejected launch configuration returns), so a failure inside a stage is -(1000 + hipError_t):
+// The kernel-selection stages (the `launch` of every row of conv_stages, conv_plan.h / conv_igemm.hip; conv_wgk3_launch) answer 1 = served,
+// 0 = the stage does not serve the problem.  hipErrorInvalidValue IS 1 (what a rejected launch configuration returns), so a failure inside a stage is -(1000 + hipError_t):
 // never mistaken for "served", and distinct from the entry points' small negative argument errors.
 #define AM_STAGE_ERR(e) (-(1000 + (int)(e)))
 #define AM_CHECK_LAUNCH_STAGE() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return AM_STAGE_ERR(e_); } while (0)

@@ -258,7 +258,9 @@ struct GaGeo { int bs, M, ntile, ny, ns, ksl, S, OS, ncls, Ed, Eh, Ew, wide; };
 //   * dense transposed convs (k4 s2) on grids that the bricks of conv_igemm pad by 1.3x or more (10^3, 12^3, 20^3: STUNet-L / H decoders),
 //     dense k3 s1 convs from 1.5x (20-wide grids).
 // (Do, Ho, Wo) is the launch's output grid.
-bool ga_geometry(GaGeo& G, int mode, int dtype, int k, int stride, int B, int Do, int Ho, int Wo, int Cin, int Cout, bool sparse, int out_bshift, int n_active) {
+bool ga_geometry(GaGeo& G, const ConvProblem& p) {
+  const int mode = p.mode, dtype = p.dtype, k = p.ksize, stride = p.stride, B = p.B, Do = p.Do, Ho = p.Ho, Wo = p.Wo, Cin = p.Cin, Cout = p.Cout;
+  const int out_bshift = p.out_bshift, n_active = p.n_active; const bool sparse = p.out_sparse;
   if (dtype != AM_DT_BF16) return false;
   const bool fwd = mode == AM_CONV_FWD && k == 3 && (stride == 1 || stride == 2);
   const bool dg1 = mode == AM_CONV_DGRAD && k == 3 && stride == 1, dg2 = mode == AM_CONV_DGRAD && k == 3 && stride == 2;
@@ -329,27 +331,34 @@ int ga_launch(ConvArgs& a, GaArgs& r, hipStream_t st) {
 
 namespace amconv {
 
-int conv_gather_rows(int mode, int dtype, int ksize, int stride, int B, int Do, int Ho, int Wo, int Cin, int Cout, int out_sparse, int out_bshift,
-                     int n_active) {
+int conv_gather_fits(const ConvProblem& p) {
   GaGeo G;
-  return ga_geometry(G, mode, dtype, ksize, stride, B, Do, Ho, Wo, Cin, Cout, out_sparse != 0, out_bshift, n_active) ? G.ntile * G.ncls : 0;
+  return ga_geometry(G, p) ? G.ntile * G.ncls : 0;
 }
 
-// returns 1 when it took the launch, 0 when the shape does not qualify, < 0 on error
-int conv_gather_launch(int mode, int dtype, int ksize, int stride, ConvArgs& a0, const int* active_list, int n_active, void* stream) {
-  const bool sparse = a0.out_mask.m != nullptr;
-  if (sparse != (a0.in_mask.m != nullptr) || (sparse && (a0.in_mask.m != a0.out_mask.m || !active_list))) return 0;
-  if (a0.ep_scale || a0.ep_res || a0.ep_act != AM_ACT_NONE || a0.nb_x) return 0;
-  if (sparse && (a0.in_mask.fd > 255 || a0.in_mask.fh > 255 || a0.in_mask.fw > 255 || a0.B > 255)) return 0;
+bool conv_gather_serves(const ConvProblem& p) {
+#ifdef AM_ABLATE
+  if (getenv("AM_CV_NORW")) return false;
+#endif
+  if (p.prenorm || p.ep || p.nbred) return false;        // (the fused input norm lives in conv_rw.hip only, the fused reduce in conv_igemm_kernel)
+  const bool sparse = p.out_sparse;
+  if (sparse != p.in_sparse || (sparse && (!p.same_mask || !p.has_list))) return false;
+  if (sparse && (p.fd > 255 || p.fh > 255 || p.fw > 255 || p.B > 255)) return false;
   GaGeo G;
-  if (!ga_geometry(G, mode, dtype, ksize, stride, a0.B, a0.Do, a0.Ho, a0.Wo, a0.Cin, a0.Cout, sparse, a0.out_mask.bs, n_active)) return 0;
-  if (a0.accumulate && a0.partials) return 0;
+  if (!ga_geometry(G, p)) return false;
+  if (p.accumulate && p.partials) return false;
   // grids and block shifts must be those the geometry assumed: source grid = S x the enumeration grid, output grid = OS x it
-  if (a0.Di != G.Ed * G.S || a0.Hi != G.Eh * G.S || a0.Wi != G.Ew * G.S) return 0;
-  if (sparse && a0.in_mask.bs != G.bs + (G.S == 2 ? 1 : 0)) return 0;
-  ConvArgs& a = a0;
+  if (p.Di != G.Ed * G.S || p.Hi != G.Eh * G.S || p.Wi != G.Ew * G.S) return false;
+  return !sparse || p.in_bshift == G.bs + (G.S == 2 ? 1 : 0);
+}
+
+int conv_gather_launch(const ConvProblem& p, ConvArgs& a, const int* active_list, void* stream, int* rows) {
+  if (!conv_gather_serves(p)) return 0;
+  const int mode = p.mode;
+  GaGeo G;
+  ga_geometry(G, p);
   GaArgs r;
-  r.plist = sparse ? active_list : nullptr; r.M = G.M; r.bs = G.bs; r.ntile = G.ntile; r.ny = G.ny; r.S = G.S; r.OS = G.OS; r.ncls = G.ncls;
+  r.plist = p.out_sparse ? active_list : nullptr; r.M = G.M; r.bs = G.bs; r.ntile = G.ntile; r.ny = G.ny; r.S = G.S; r.OS = G.OS; r.ncls = G.ncls;
   r.Ed = G.Ed; r.Eh = G.Eh; r.Ew = G.Ew; r.wide = G.wide;
   if (G.wide) {
     // the transposed conv's data gradient (P/decoder3D.py:16-17 ConvTranspose3d k4 s2 p1): dx[q] = sum_t W_t dy[2q + t - 1], t in 0..3 per dim
@@ -369,9 +378,9 @@ int conv_gather_launch(int mode, int dtype, int ksize, int stride, ConvArgs& a0,
   } else {
     // two-class-stride plans: conv_plan.h lists, per output parity class, the taps and their source shifts on the coarse grid
     Plan P;
-    P.a = a0;
+    P.a = a;
     P.bd = 4; P.bh = 4; P.bw = 16; P.nt_tile = 64;        // (only the tap table of the plan is used)
-    const int rc = build_plan(P, mode, ksize, stride);
+    const int rc = build_plan(P, mode, p.ksize, p.stride);
     if (rc) return rc;
     if (P.a.OS != 2 || P.a.tap_begin[8] > 64) return 0;
     for (int c = 0; c <= 8; ++c) r.cbeg[c] = P.a.tap_begin[c];
@@ -384,6 +393,7 @@ int conv_gather_launch(int mode, int dtype, int ksize, int stride, ConvArgs& a0,
     }
   }
   hipStream_t st = (hipStream_t)stream;
+  if (rows) *rows = G.ntile * G.ncls;
   if (G.ns == 8) return ga_launch<8, 4>(a, r, st);
   return G.ksl == 8 ? ga_launch<4, 8>(a, r, st) : G.ksl == 4 ? ga_launch<4, 4>(a, r, st) : ga_launch<4, 2>(a, r, st);
 }

@@ -569,14 +569,14 @@ int launch(Plan& P, hipStream_t st) {
   ConvArgs& a = P.a;
   constexpr auto kern = conv_igemm_kernel<T, BD, BH, BW, NS, NIT, TGS, HR, NB, HT>;
   if (P.lds > 160 * 1024) return -3;
-  AM_HIP(am_lds_optin<kern>());
+  AM_HIP_STAGE(am_lds_optin<kern>());
   const unsigned nbrick = a.plist ? (unsigned)a.nlive : (unsigned)(a.B * a.nbd * a.nbh * a.nbw);
   a.ny = (a.Cout + 16 * NS - 1) / (16 * NS);
   const unsigned nsib = (unsigned)(a.ny * a.nclass);
   dim3 grid(nsib > 1 ? ((nbrick + 7) / 8) * 8 * nsib : nbrick, 1, 1);       // (channel tiles and parity classes folded into x, see the kernel)
   AM_LAUNCH(kern, grid, dim3(256), P.lds, st, a);
-  AM_CHECK_LAUNCH();
-  return 0;
+  AM_CHECK_LAUNCH_STAGE();
+  return 1;
 }
 
 template <typename T, int NS>
@@ -650,8 +650,14 @@ static int brick_shape(int os, int qh, int qw, bool out_sparse, int out_bshift, 
 // the channel tile (2x the workgroups, each still 4 subtiles x 2 channel tiles per wave = 24 MFMAs per weight group); only if
 // that still leaves most CUs idle do they drop to 64-voxel bricks (6 MFMAs per barrier: measured 151 us for the 512->512 conv
 // at 8^3 where the 256-voxel brick x 32 channels takes a third of that).
-static int pick_tiling(int os, int B, int qd, int qh, int qw, int Cout, bool out_sparse, int out_bshift, int* bd, int* bh, int* bw, int* nt, bool big_ok = true) {
-  int shape = brick_shape(os, qh, qw, out_sparse, out_bshift, bd, bh, bw);
+static int pick_tiling(const ConvProblem& p, int* bd, int* bh, int* bw, int* nt) {
+  const int os = p.mode == AM_CONV_DGRAD ? p.stride : (p.mode == AM_CONVT_FWD ? 2 : 1), B = p.B, Cout = p.Cout;
+  const int qd = (p.Do + os - 1) / os, qh = (p.Ho + os - 1) / os, qw = (p.Wo + os - 1) / os; const bool out_sparse = p.out_sparse;
+  bool big_ok = p.dtype == AM_DT_BF16;           // 512-voxel transposed-conv bricks: bf16 only (the fp32 instantiation needs 258 VGPRs and spills)
+#ifdef AM_ABLATE
+  { const char* e_ = getenv("AM_CV_NOBIG"); if (e_ && atoi(e_)) big_ok = false; }
+#endif
+  int shape = brick_shape(os, qh, qw, out_sparse, p.out_bshift, bd, bh, bw);
   *nt = Cout <= 32 ? 32 : 64;
   const long q = (long)qd * qh * qw;
   // (bricks counted per dimension: a 12^3 grid is 3 x 2 x 2 = 12 bricks of 4x8x8, not ceil(1728 / 256) = 7)
@@ -676,140 +682,121 @@ extern "C" int am_packed_dims(int dtype, int rows, int k, int* rows_padded, int*
   return 0;
 }
 
-extern "C" int am_conv3d_partials_rows(int mode, int dtype, int ksize, int stride, int B, int Do, int Ho, int Wo, int Cin, int Cout, int out_sparse,
-                                       int out_bshift, int n_active, int* rows) {
-  const int os = (mode == AM_CONV_DGRAD) ? stride : (mode == AM_CONVT_FWD ? 2 : 1);
-  const int qd = (Do + os - 1) / os, qh = (Ho + os - 1) / os, qw = (Wo + os - 1) / os;
+// ---- the generic stage: every launch no persistent kernel takes.  One row per brick of the q grid and parity class (live bricks only with a list)
+int amconv::conv_igemm_fits(const ConvProblem& p) {
+  const int os = p.mode == AM_CONV_DGRAD ? p.stride : (p.mode == AM_CONVT_FWD ? 2 : 1);
   int bd, bh, bw, nt;
-  pick_tiling(os, B, qd, qh, qw, Cout, out_sparse != 0, out_bshift, &bd, &bh, &bw, &nt, dtype == AM_DT_BF16);   // (512-voxel bricks: bf16 only, as in conv3d_impl)
-  *rows = B * ((qd + bd - 1) / bd) * ((qh + bh - 1) / bh) * ((qw + bw - 1) / bw) * (os == 2 ? 8 : 1);
-  // upper bound over the kernels a launch of this shape may take (am_conv3d reports the rows it actually wrote)
-  const int rw = conv_rw_rows(mode, dtype, ksize, stride, B, Do, Ho, Wo, Cin, Cout, out_sparse, out_bshift, n_active);
-  if (rw > *rows) *rows = rw;
-  const int rg = conv_gather_rows(mode, dtype, ksize, stride, B, Do, Ho, Wo, Cin, Cout, out_sparse, out_bshift, n_active);
-  if (rg > *rows) *rows = rg;
-  const int rk = conv_k3_rows(mode, dtype, ksize, stride, B, Do, Ho, Wo, Cin, Cout, out_sparse);
-  if (rk > *rows) *rows = rk;
-  return 0;
+  pick_tiling(p, &bd, &bh, &bw, &nt);
+  return p.B * ((p.Do + os * bd - 1) / (os * bd)) * ((p.Ho + os * bh - 1) / (os * bh)) * ((p.Wo + os * bw - 1) / (os * bw)) * (os == 2 ? 8 : 1);
 }
 
-extern "C" int am_conv3d_uses_k3(int mode, int dtype, int ksize, int stride, int B, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout,
-                                 int has_masks, int accumulate, int fused_epilogue, int want_partials) {
-  return conv_k3_which(mode, dtype, ksize, stride, B, Di, Hi, Wi, Do, Ho, Wo, Cin, Cout, has_masks, accumulate, fused_epilogue, want_partials);
-}
+bool amconv::conv_igemm_serves(const ConvProblem& p) { return !p.prenorm; }      // (the fused input norm lives in conv_rw.hip only)
 
-static int conv3d_impl(int mode, int dtype, int ksize, int stride, const void* x, const void* w_packed,
-                       const float* bias, void* y, int B, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo,
-                       int Cout, const uint8_t* in_mask, int in_bshift, const uint8_t* out_mask, int out_bshift,
-                       int fd, int fh, int fw, int accumulate, float* partials, const float* ep_scale, const float* ep_shift,
-                       const void* ep_res, int ep_act, const int32_t* active_list, int n_active, int* partial_rows_written,
-                       const void* nb_x, const float* nb_scale, const float* nb_shift, int nb_act, void* stream,
-                       const float* in_scale = nullptr, const float* in_shift = nullptr, int in_act = 0) {
-  if (Cin % 8 || Cout % 8) return -1;
-  if (ep_scale && !ep_shift) return -1;
+int amconv::conv_igemm_launch(const ConvProblem& p, ConvArgs& a0, const int* active_list, void* stream, int* rows) {
+  if (!conv_igemm_serves(p)) return 0;
   Plan P;
-  ConvArgs& a = P.a;
-  a.stats_sum_only = (accumulate & AM_CONV_PARTIALS_SUM_ONLY) ? 1 : 0;      // (a hint: every kernel but conv_k3's fills both columns anyway)
-  accumulate &= 1;
-  a.nb_x = nb_x; a.nb_scale = nb_scale; a.nb_shift = nb_shift; a.nb_act = nb_act;
-  a.in_scale = in_scale; a.in_shift = in_shift; a.in_act = in_act;
-  // ---- thin layers with everything resident in LDS: conv_rw.hip ----
-  {
-    a.x = x; a.w = w_packed; a.bias = bias; a.y = y; a.partials = partials;
-    a.ep_scale = ep_scale; a.ep_shift = ep_scale ? ep_shift : nullptr; a.ep_res = ep_res; a.ep_act = ep_act;
-    a.B = B; a.Di = Di; a.Hi = Hi; a.Wi = Wi; a.Cin = Cin; a.Do = Do; a.Ho = Ho; a.Wo = Wo; a.Cout = Cout;
-    am_packed_dims(dtype, Cout, Cin, &a.Coutp, &a.Cinp);
-    a.w_bytes = ksize * ksize * ksize * a.Coutp * a.Cinp * (dtype == AM_DT_BF16 ? 2 : 4);
-    a.in_mask = MaskView{in_mask, fd, fh, fw, in_bshift};
-    a.out_mask = MaskView{out_mask, fd, fh, fw, out_bshift};
-    a.accumulate = accumulate; a.nt_store = 0; a.brick_in_patch = 0; a.hreuse = 0;
-#ifdef AM_ABLATE
-    { const char* e = getenv("AM_CV_DBG"); a.dbg = e ? atoi(e) : 0; }
-    if (getenv("AM_CV_NORW")) goto generic;
-#endif
-    a.plist = nullptr;
-    if (!in_scale && mode == AM_CONVT_FWD && !partials) {   // dense transposed convs at decoder sizes: the persistent kernel's transposed instantiation
-      const int rt = conv_k3t_launch(mode, dtype, ksize, stride, a, stream);
-      if (rt < 0) return rt;
-      if (rt == 1) return 0;
-    }
-    if (!in_scale) {                               // dense k3 s1 at decoder sizes: the persistent LDS-DMA kernel (conv_k3.hip)
-      const int rk = conv_k3_launch(mode, dtype, ksize, stride, a, stream, partial_rows_written);
-      if (rk < 0) return rk;
-      if (rk == 1) return 0;
-    }
-    const int rc = nb_x ? 0 : conv_rw_launch(mode, dtype, ksize, stride, a, active_list, n_active, stream);   // (the fused reduce lives in conv_igemm_kernel only)
-    if (rc < 0) return rc;
-    if (rc == 1) {
-      if (partial_rows_written) *partial_rows_written = conv_rw_rows(mode, dtype, ksize, stride, B, Do, Ho, Wo, Cin, Cout, out_mask != nullptr, out_bshift, n_active);
-      return 0;
-    }
-    if (in_scale) return -7;                       // (the fused input norm lives in conv_rw.hip only: am_conv3d_prenorm_supported says when)
-    const int rg = conv_gather_launch(mode, dtype, ksize, stride, a, active_list, n_active, stream);   // deep block-sparse levels: rows = active voxels
-    if (rg < 0) return rg;
-    if (rg == 1) {
-      if (partial_rows_written) *partial_rows_written = conv_gather_rows(mode, dtype, ksize, stride, B, Do, Ho, Wo, Cin, Cout, out_mask != nullptr, out_bshift, n_active);
-      return 0;
-    }
-  }
-#ifdef AM_ABLATE
-generic:
-#endif
-  const int os_ = (mode == AM_CONV_DGRAD) ? stride : (mode == AM_CONVT_FWD ? 2 : 1);
-  bool big_ok = dtype == AM_DT_BF16;             // 512-voxel transposed-conv bricks: bf16 only (the fp32 instantiation needs 258 VGPRs and spills)
-#ifdef AM_ABLATE
-  { const char* e_ = getenv("AM_CV_NOBIG"); if (e_ && atoi(e_)) big_ok = false; }
-#endif
-  int shape = pick_tiling(os_, B, (Do + os_ - 1) / os_, (Ho + os_ - 1) / os_, (Wo + os_ - 1) / os_, Cout, out_mask != nullptr, out_bshift,
-                          &P.bd, &P.bh, &P.bw, &P.nt_tile, big_ok);
-  int rc = build_plan(P, mode, ksize, stride);
+  ConvArgs& a = P.a = a0;
+  const int shape = pick_tiling(p, &P.bd, &P.bh, &P.bw, &P.nt_tile);
+  const int rc = build_plan(P, p.mode, p.ksize, p.stride);
   if (rc) return rc;
   // k1 s2 data gradient that ACCUMULATES into y: only output parity (0, 0, 0) has a tap, the other 7 classes add nothing -- launch class 0
   // alone (as siblings in blockIdx.x the 7 idle classes sat between the live workgroups and the launch ran at the dispatcher's pace:
   // 64 -> 32 @128^3 took 0.48 ms for 0.1 ms of work)
-  if (a.OS == 2 && accumulate && !partials && a.tap_begin[1] > a.tap_begin[0] && a.tap_begin[8] == a.tap_begin[1]) a.nclass = 1;
-  a.x = x; a.w = w_packed; a.bias = bias; a.y = y; a.partials = partials;
-  a.ep_scale = ep_scale; a.ep_shift = ep_scale ? ep_shift : nullptr; a.ep_res = ep_res; a.ep_act = ep_act;
-  a.B = B; a.Di = Di; a.Hi = Hi; a.Wi = Wi; a.Cin = Cin; a.Do = Do; a.Ho = Ho; a.Wo = Wo; a.Cout = Cout;
-  am_packed_dims(dtype, Cout, Cin, &a.Coutp, &a.Cinp);
-  a.w_bytes = ksize * ksize * ksize * a.Coutp * a.Cinp * (dtype == AM_DT_BF16 ? 2 : 4);
-  if ((size_t)24 * Hi * Wi * Cin * 4 >= 0x7fffff00ull) return -5;   // the <= 24 source planes a brick spans must stay below 2 GB (32-bit offsets)
-  const int Qd = (Do + a.OS - 1) / a.OS, Qh = (Ho + a.OS - 1) / a.OS, Qw = (Wo + a.OS - 1) / a.OS;
+  if (a.OS == 2 && p.accumulate && !p.partials && a.tap_begin[1] > a.tap_begin[0] && a.tap_begin[8] == a.tap_begin[1]) a.nclass = 1;
+  if ((size_t)24 * p.Hi * p.Wi * p.Cin * 4 >= 0x7fffff00ull) return -5;   // the <= 24 source planes a brick spans must stay below 2 GB (32-bit offsets)
+  const int Qd = (p.Do + a.OS - 1) / a.OS, Qh = (p.Ho + a.OS - 1) / a.OS, Qw = (p.Wo + a.OS - 1) / a.OS;
   a.nbd = (Qd + P.bd - 1) / P.bd; a.nbh = (Qh + P.bh - 1) / P.bh; a.nbw = (Qw + P.bw - 1) / P.bw;
-  a.in_mask = MaskView{in_mask, fd, fh, fw, in_bshift};
-  a.out_mask = MaskView{out_mask, fd, fh, fw, out_bshift};
-  a.accumulate = accumulate;
-  a.plist = nullptr; a.pbd = a.pbh = a.pbw = a.nlive = 0;
   {
-    const int qblock = out_mask ? ((1 << out_bshift) / a.OS) : 0;
+    const int qblock = p.out_sparse ? ((1 << p.out_bshift) / a.OS) : 0;
     a.brick_in_patch = qblock > 0 && qblock % P.bd == 0 && qblock % P.bh == 0 && qblock % P.bw == 0;
     // (the list is am_mask_compact of this launch's OUT mask; whole patches inside the grid)
-    bool listed = a.brick_in_patch && active_list && n_active > 0 && fd <= 255 && fh <= 255 && fw <= 255 && B <= 255 &&
-                  Qd == fd * qblock && Qh == fh * qblock && Qw == fw * qblock;
+    bool listed = a.brick_in_patch && active_list && p.n_active > 0 && p.fd <= 255 && p.fh <= 255 && p.fw <= 255 && p.B <= 255 &&
+                  Qd == p.fd * qblock && Qh == p.fh * qblock && Qw == p.fw * qblock;
 #ifdef AM_ABLATE
     { const char* e = getenv("AM_CV_NOLIST"); if (e && atoi(e)) listed = false; }
 #endif
     if (listed) {
       a.plist = active_list; a.pbd = qblock / P.bd; a.pbh = qblock / P.bh; a.pbw = qblock / P.bw;
-      a.nlive = n_active * a.pbd * a.pbh * a.pbw;
+      a.nlive = p.n_active * a.pbd * a.pbh * a.pbw;
     }
   }
-#ifdef AM_ABLATE
-  { const char* e = getenv("AM_CV_DBG"); a.dbg = e ? atoi(e) : 0; }
-#endif
-  if (partials && dtype == AM_DT_BF16) {                 // the bf16 statistics epilogue lays the output tile out in LDS: [voxel][NT channels + 32 B]
+  if (p.partials && p.dtype == AM_DT_BF16) {             // the bf16 statistics epilogue lays the output tile out in LDS: [voxel][NT channels + 32 B]
     const size_t tile = (size_t)P.bd * P.bh * P.bw * (P.nt_tile * 2 + 32);
     if (P.lds < tile) P.lds = tile;                      // (only when asked for: 512-voxel bricks would lose their second workgroup per CU to it)
   }
-  if (nb_x) {                                            // two [voxel][channel] tiles in the epilogue (g and the norm's input)
+  if (p.nbred) {                                         // two [voxel][channel] tiles in the epilogue (g and the norm's input)
     const size_t tiles = (size_t)P.bd * P.bh * P.bw * (P.nt_tile * 4 + 32);
     if (P.lds < tiles) P.lds = tiles;
   }
   // outputs far larger than the 256 MB Infinity Cache bypass it (measured +2.5 % on the 1 GB decoder tensors: the halo re-reads keep L2)
-  a.nt_store = ((size_t)B * Do * Ho * Wo * Cout * 2 >= ((size_t)384 << 20) && !accumulate) || AM_DBG(a, 8);
+  a.nt_store = ((size_t)p.B * p.Do * p.Ho * p.Wo * p.Cout * 2 >= ((size_t)384 << 20) && !p.accumulate) || AM_DBG(a, 8);
   hipStream_t st = (hipStream_t)stream;
-  if (partial_rows_written) *partial_rows_written = (a.plist ? a.nlive : a.B * a.nbd * a.nbh * a.nbw) * a.nclass;
-  return dtype == AM_DT_BF16 ? dispatch<bf16_t>(P, shape, st) : dtype == AM_DT_F32S ? dispatch<f32s_t>(P, shape, st) : dispatch<float>(P, shape, st);
+  if (rows) *rows = (a.plist ? a.nlive : a.B * a.nbd * a.nbh * a.nbw) * a.nclass;
+  return p.dtype == AM_DT_BF16 ? dispatch<bf16_t>(P, shape, st) : p.dtype == AM_DT_F32S ? dispatch<f32s_t>(P, shape, st) : dispatch<float>(P, shape, st);
+}
+
+// Kernel selection: the first stage that serves a problem takes the launch.  The queries below walk the same table.
+#define AM_STAGE_ROW(name_) {#name_, name_##_fits, name_##_serves, name_##_launch}
+static const ConvStage conv_stages[] = {AM_STAGE_ROW(conv_k3t), AM_STAGE_ROW(conv_k3), AM_STAGE_ROW(conv_rw), AM_STAGE_ROW(conv_gather), AM_STAGE_ROW(conv_igemm)};
+
+// A problem starts as its geometry, `ConvProblem p{mode, dtype, ksize, stride, B, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout}` (the rest zero).
+// A query knows one `sparse` flag: both sides masked by one tensor, its list at hand
+static void query_masks(ConvProblem& p, bool sparse, int in_bshift, int out_bshift, int n_active) {
+  p.in_sparse = p.out_sparse = sparse; p.same_mask = p.has_list = true;
+  p.in_bshift = in_bshift; p.out_bshift = out_bshift; p.n_active = n_active;
+}
+
+extern "C" int am_conv3d_partials_rows(int mode, int dtype, int ksize, int stride, int B, int Do, int Ho, int Wo, int Cin, int Cout, int out_sparse,
+                                       int out_bshift, int n_active, int* rows) {
+  ConvProblem p{mode, dtype, ksize, stride, B, Do, Ho, Wo, Cin, Do, Ho, Wo, Cout};      // (fits reads the output grid only)
+  query_masks(p, out_sparse != 0, out_bshift, out_bshift, n_active);
+  // upper bound over the kernels a launch of this shape may take (am_conv3d reports the rows it actually wrote)
+  *rows = 0;
+  for (const ConvStage& s : conv_stages) { const int r = s.fits(p); if (r > *rows) *rows = r; }
+  return 0;
+}
+
+extern "C" int am_conv3d_uses_k3(int mode, int dtype, int ksize, int stride, int B, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout,
+                                 int has_masks, int accumulate, int fused_epilogue, int want_partials) {
+  ConvProblem p{mode, dtype, ksize, stride, B, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout};
+  query_masks(p, has_masks != 0, 0, 0, 0);
+  p.accumulate = accumulate != 0; p.ep = fused_epilogue != 0; p.partials = want_partials != 0;
+  for (const ConvStage& s : conv_stages)
+    if (s.serves(p)) return s.launch == conv_k3t_launch ? 2 : s.launch == conv_k3_launch ? 1 : 0;
+  return 0;
+}
+
+// The caller's arguments, written ONCE before the stages are walked: pointers, shape, packed dimensions, masks.  The entry points add
+// their own optional operands (epilogue / norm-backward reduce / input norm); a stage adds only what belongs to its kernel.
+static ConvArgs fill_args(const ConvProblem& p, const void* x, const void* w_packed, const float* bias, void* y, float* partials, const uint8_t* in_mask,
+                          int in_bshift, const uint8_t* out_mask, int out_bshift, int fd, int fh, int fw, int accumulate) {
+  ConvArgs a{};
+  a.x = x; a.w = w_packed; a.bias = bias; a.y = y; a.partials = partials;
+  a.B = p.B; a.Di = p.Di; a.Hi = p.Hi; a.Wi = p.Wi; a.Cin = p.Cin; a.Do = p.Do; a.Ho = p.Ho; a.Wo = p.Wo; a.Cout = p.Cout;
+  am_packed_dims(p.dtype, p.Cout, p.Cin, &a.Coutp, &a.Cinp);
+  a.w_bytes = p.ksize * p.ksize * p.ksize * a.Coutp * a.Cinp * (p.dtype == AM_DT_BF16 ? 2 : 4);
+  a.in_mask = MaskView{in_mask, fd, fh, fw, in_bshift};
+  a.out_mask = MaskView{out_mask, fd, fh, fw, out_bshift};
+  a.accumulate = accumulate & 1; a.stats_sum_only = (accumulate & AM_CONV_PARTIALS_SUM_ONLY) ? 1 : 0;      // (a hint: every kernel but conv_k3's fills both columns anyway)
+#ifdef AM_ABLATE
+  { const char* e = getenv("AM_CV_DBG"); a.dbg = e ? atoi(e) : 0; }
+#endif
+  return a;
+}
+
+// p holds the geometry; what selection needs of the pointers and options arrives here, then the first stage that serves takes the launch
+static int conv3d_impl(ConvProblem& p, ConvArgs& a, const int* active_list, int n_active, void* stream, int* rows) {
+  if (p.Cin % 8 || p.Cout % 8) return -1;
+  p.in_sparse = a.in_mask.m != nullptr; p.out_sparse = a.out_mask.m != nullptr; p.same_mask = a.in_mask.m == a.out_mask.m;
+  p.in_bshift = a.in_mask.bs; p.out_bshift = a.out_mask.bs; p.fd = a.in_mask.fd; p.fh = a.in_mask.fh; p.fw = a.in_mask.fw;
+  p.has_list = active_list != nullptr; p.n_active = n_active;
+  p.accumulate = a.accumulate != 0; p.sum_only = a.stats_sum_only != 0; p.partials = a.partials != nullptr;
+  p.ep = a.ep_scale || a.ep_res || a.ep_act != AM_ACT_NONE; p.nbred = a.nb_x != nullptr; p.prenorm = a.in_scale != nullptr;
+  for (const ConvStage& s : conv_stages) {
+    const int rc = s.launch(p, a, active_list, stream, rows);
+    if (rc) return rc == 1 ? 0 : rc;
+  }
+  return -7;                                     // no stage serves: a fused input norm on a launch conv_rw.hip does not take (am_conv3d_prenorm_supported says when)
 }
 
 extern "C" int am_conv3d(int mode, int dtype, int ksize, int stride, const void* x, const void* w_packed,
@@ -818,19 +805,25 @@ extern "C" int am_conv3d(int mode, int dtype, int ksize, int stride, const void*
                          int fd, int fh, int fw, int accumulate, float* partials, const float* ep_scale, const float* ep_shift,
                          const void* ep_res, int ep_act, const int32_t* active_list, int n_active, int* partial_rows_written,
                          void* stream) {
-  return conv3d_impl(mode, dtype, ksize, stride, x, w_packed, bias, y, B, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout, in_mask, in_bshift, out_mask,
-                     out_bshift, fd, fh, fw, accumulate, partials, ep_scale, ep_shift, ep_res, ep_act, active_list, n_active,
-                     partial_rows_written, nullptr, nullptr, nullptr, 0, stream);
+  if (ep_scale && !ep_shift) return -1;
+  ConvProblem p{mode, dtype, ksize, stride, B, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout};
+  ConvArgs a = fill_args(p, x, w_packed, bias, y, partials, in_mask, in_bshift, out_mask, out_bshift, fd, fh, fw, accumulate);
+  a.ep_scale = ep_scale; a.ep_shift = ep_scale ? ep_shift : nullptr; a.ep_res = ep_res; a.ep_act = ep_act;
+  return conv3d_impl(p, a, active_list, n_active, stream, partial_rows_written);
 }
 
 // Forward convolution of act(x * in_scale + in_shift) -- a (pooled sparse Instance)Norm + activation folded into the consumer's source
 // staging, so that the normalised map is never written or read (the EMA teacher's stage-0 conv2 and every encoder pass that keeps no
 // tape: P/STUNet_head.py:96-103 `y = LReLU(IN(conv1 x)); conv2(y)`).  Inactive / out-of-volume source rows stay zero, as the dense-conv-
-// then-mask semantics of P/encoder3D.py:12-15 has them.  Served by conv_rw.hip only (bf16, Cin <= 32, k3): am_conv3d_prenorm_supported.
+// then-mask semantics of P/encoder3D.py:12-15 has them.  Served by conv_rw.hip only (bf16, Cin <= 32, k3): am_conv3d_prenorm_supported
+// is that stage's own `serves`.
 extern "C" int am_conv3d_prenorm_supported(int mode, int dtype, int ksize, int stride, int B, int Do, int Ho, int Wo, int Cin, int Cout,
                                            int sparse, int in_bshift, int out_bshift, int n_active) {
-  if (mode != AM_CONV_FWD || !sparse || n_active <= 0 || in_bshift != out_bshift + (stride == 2 ? 1 : 0)) return 0;
-  return conv_rw_rows(mode, dtype, ksize, stride, B, Do, Ho, Wo, Cin, Cout, sparse, out_bshift, n_active) > 0 ? 1 : 0;
+  if (!sparse) return 0;                         // (am_conv3d_prenorm takes a mask and its list)
+  ConvProblem p{mode, dtype, ksize, stride, B, Do, Ho, Wo, Cin, Do, Ho, Wo, Cout};
+  query_masks(p, true, in_bshift, out_bshift, n_active);
+  p.prenorm = true;
+  return conv_rw_serves(p) ? 1 : 0;
 }
 
 extern "C" int am_conv3d_prenorm(int mode, int dtype, int ksize, int stride, const void* x, const void* w_packed, const float* bias, void* y,
@@ -839,9 +832,10 @@ extern "C" int am_conv3d_prenorm(int mode, int dtype, int ksize, int stride, con
                                  int in_act, const int32_t* active_list, int n_active, int* partial_rows_written, void* stream) {
   if (!in_scale || !in_shift || !mask || !active_list) return -1;
   if (in_act != AM_ACT_NONE && in_act != AM_ACT_LRELU && in_act != AM_ACT_RELU6) return -1;
-  return conv3d_impl(mode, dtype, ksize, stride, x, w_packed, bias, y, B, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout, mask, in_bshift, mask, out_bshift,
-                     fd, fh, fw, 0, partials, nullptr, nullptr, nullptr, AM_ACT_NONE, active_list, n_active, partial_rows_written,
-                     nullptr, nullptr, nullptr, 0, stream, in_scale, in_shift, in_act);
+  ConvProblem p{mode, dtype, ksize, stride, B, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout};
+  ConvArgs a = fill_args(p, x, w_packed, bias, y, partials, mask, in_bshift, mask, out_bshift, fd, fh, fw, 0);
+  a.in_scale = in_scale; a.in_shift = in_shift; a.in_act = in_act;
+  return conv3d_impl(p, a, active_list, n_active, stream, partial_rows_written);
 }
 
 // A data-gradient (or any) convolution whose output y is the gradient wrt a = act(nb_x * nb_scale + nb_shift), the output of a
@@ -856,7 +850,8 @@ extern "C" int am_conv3d_nbred(int mode, int dtype, int ksize, int stride, const
   if (dtype != AM_DT_BF16 || !partials || !nb_x) return -1;
   if (nb_act != AM_ACT_NONE && (!nb_scale || !nb_shift)) return -1;
   if (nb_act != AM_ACT_NONE && nb_act != AM_ACT_LRELU && nb_act != AM_ACT_RELU6) return -1;
-  return conv3d_impl(mode, dtype, ksize, stride, x, w_packed, nullptr, y, B, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout, in_mask, in_bshift, out_mask,
-                     out_bshift, fd, fh, fw, accumulate, partials, nullptr, nullptr, nullptr, AM_ACT_NONE, nullptr, 0,
-                     partial_rows_written, nb_x, nb_scale, nb_shift, nb_act, stream);
+  ConvProblem p{mode, dtype, ksize, stride, B, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout};
+  ConvArgs a = fill_args(p, x, w_packed, nullptr, y, partials, in_mask, in_bshift, out_mask, out_bshift, fd, fh, fw, accumulate);
+  a.nb_x = nb_x; a.nb_scale = nb_scale; a.nb_shift = nb_shift; a.nb_act = nb_act;
+  return conv3d_impl(p, a, nullptr, 0, stream, partial_rows_written);
 }

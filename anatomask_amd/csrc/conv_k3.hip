@@ -565,73 +565,68 @@ static bool k3_qualifies(int mode, int dtype, int ksize, int stride, int B, int 
   if (Cin % 32 || Cout % 32 || D % KBD || H % KBH || W % KBW) return false;
   // `Item` packs the sample index and the three brick indices into 8-bit fields (IT_B / IT_Q0*): larger launches go to conv_igemm.hip
   if (B > 255 || D / KBD > 255 || H / KBH > 255 || W / KBW > 255) return false;
-  return true;
+  return k3_units(B, D, H, W, Cout) >= K3_MIN_UNITS;
 }
 
 // rows of partial sums a launch of this kernel writes on the current device (8 per workgroup), or 0 when the shape does not qualify
-int conv_k3_rows(int mode, int dtype, int ksize, int stride, int B, int D, int H, int W, int Cin, int Cout, int masks) {
-  if (!k3_qualifies(mode, dtype, ksize, stride, B, D, H, W, Cin, Cout, masks != 0)) return 0;
-  const int units = k3_units(B, D, H, W, Cout);
-  if (units < K3_MIN_UNITS) return 0;
-  return k3_grid(units, Cout) * 8;
+int conv_k3_fits(const ConvProblem& p) {
+  if (!k3_qualifies(p.mode, p.dtype, p.ksize, p.stride, p.B, p.Do, p.Ho, p.Wo, p.Cin, p.Cout, p.in_sparse || p.out_sparse)) return 0;
+  return k3_grid(k3_units(p.B, p.Do, p.Ho, p.Wo, p.Cout), p.Cout) * 8;
 }
 
-// Every condition under which conv_k3_launch / conv_k3t_launch take a launch, as ONE predicate each: the launchers decide by them, and
-// conv_k3_which (am_conv3d_uses_k3) answers with them, so a test that asks which kernel serves a launch gets the launcher's own decision.
-static bool k3_serves(int mode, int dtype, int ksize, int stride, int B, int Di, int Hi, int Wi, int Do, int Ho, int Wo, int Cin, int Cout,
-                      bool masks, bool accumulate, bool nbred, bool ep, bool partials) {
-  if (!k3_qualifies(mode, dtype, ksize, stride, B, Di, Hi, Wi, Cin, Cout, masks)) return false;
-  if (accumulate || nbred) return false;
-  if (Di != Do || Hi != Ho || Wi != Wo) return false;
-  if ((size_t)(KED + 1) * Hi * Wi * Cin * 2 >= 0x7fffff00ull) return false;     // the brick's planes must stay below 2 GB (32-bit offsets)
-  if (k3_units(B, Di, Hi, Wi, Cout) < K3_MIN_UNITS) return false;
-  if (ep && partials) return false;                // (no caller fuses a store epilogue AND asks for statistics: conv_igemm.hip serves it)
+// Every condition under which the stages take a launch, as ONE predicate each: the launchers decide by them, and am_conv3d_uses_k3
+// answers with them, so a test that asks which kernel serves a launch gets the launcher's own decision.
+bool conv_k3_serves(const ConvProblem& p) {
+#ifdef AM_ABLATE
+  if (getenv("AM_CV_NORW") || getenv("AM_CV_NOK3")) return false;
+  { const char* e_ = getenv("AM_K3_NO32"); if (e_ && atoi(e_) && p.Cout % 64) return false; }
+#endif
+  if (!conv_k3_fits(p) || p.prenorm || p.accumulate || p.nbred) return false;
+  if (p.Di != p.Do || p.Hi != p.Ho || p.Wi != p.Wo) return false;
+  if ((size_t)(KED + 1) * p.Hi * p.Wi * p.Cin * 2 >= 0x7fffff00ull) return false;     // the brick's planes must stay below 2 GB (32-bit offsets)
+  if (p.ep && p.partials) return false;            // (no caller fuses a store epilogue AND asks for statistics: conv_igemm.hip serves it)
   return true;
 }
 
-static bool k3t_serves(int mode, int dtype, int ksize, int stride, int B, int Di, int Hi, int Wi, int Do, int Ho, int Wo, int Cin, int Cout,
-                       bool masks, bool accumulate, bool nbred, bool ep, bool partials) {
-  if (mode != AM_CONVT_FWD || dtype != AM_DT_BF16 || ksize != 4 || stride != 2 || masks) return false;
-  if (accumulate || nbred || partials || ep) return false;
-  if (Cin % 32 || Cin < 64 || Cout % 64 || Di % KBD || Hi % KBH || Wi % KBW) return false;      // (>= 2 slabs: the deferred stores of a class ride in the next one's first item)
-  if (Do != 2 * Di || Ho != 2 * Hi || Wo != 2 * Wi) return false;
-  if (B > 255 || Di / KBD > 255 || Hi / KBH > 255 || Wi / KBW > 255) return false;
-  if ((size_t)(KED + 1) * Hi * Wi * Cin * 2 >= 0x7fffff00ull || (size_t)16 * Wo * Cout * 2 >= 0x7fffff00ull) return false;
-  return k3_units(B, Di, Hi, Wi, Cout) >= K3_MIN_UNITS;
-}
-
-// 0: neither, 1: conv_k3_kernel, 2: its transposed instantiation -- for an am_conv3d launch (no fused input norm, no norm-backward reduce)
-int conv_k3_which(int mode, int dtype, int ksize, int stride, int B, int Di, int Hi, int Wi, int Do, int Ho, int Wo, int Cin, int Cout,
-                  int masks, int accumulate, int ep, int partials) {
-  if (k3t_serves(mode, dtype, ksize, stride, B, Di, Hi, Wi, Do, Ho, Wo, Cin, Cout, masks != 0, accumulate != 0, false, ep != 0, partials != 0)) return 2;
-  if (k3_serves(mode, dtype, ksize, stride, B, Di, Hi, Wi, Do, Ho, Wo, Cin, Cout, masks != 0, accumulate != 0, false, ep != 0, partials != 0)) return 1;
-  return 0;
-}
-
-int conv_k3_launch(int mode, int dtype, int ksize, int stride, ConvArgs& c, void* stream, int* rows) {
-  if (!k3_serves(mode, dtype, ksize, stride, c.B, c.Di, c.Hi, c.Wi, c.Do, c.Ho, c.Wo, c.Cin, c.Cout, c.in_mask.m || c.out_mask.m, c.accumulate != 0,
-                 c.nb_x != nullptr, c.ep_scale || c.ep_res || c.ep_act != AM_ACT_NONE, c.partials != nullptr)) return 0;
-  const int dev = am_device();
-  const int units = k3_units(c.B, c.Di, c.Hi, c.Wi, c.Cout), G = k3_grid(units, c.Cout, dev);
+// ConvTranspose3d k4 s2 p1 on the kernel's transposed instantiation.  It takes no launch that asks for statistics: no rows
+int conv_k3t_fits(const ConvProblem&) { return 0; }
+bool conv_k3t_serves(const ConvProblem& p) {
 #ifdef AM_ABLATE
-  if (getenv("AM_CV_NOK3")) return 0;
-  { const char* e_ = getenv("AM_K3_NO32"); if (e_ && atoi(e_) && c.Cout % 64) return 0; }
+  if (getenv("AM_CV_NORW")) return false;
+  { const char* e_ = getenv("AM_CV_NOK3T"); if (e_ && atoi(e_)) return false; }
 #endif
-  K3Args a;
+  if (p.mode != AM_CONVT_FWD || p.dtype != AM_DT_BF16 || p.ksize != 4 || p.stride != 2 || p.in_sparse || p.out_sparse) return false;
+  if (p.prenorm || p.accumulate || p.nbred || p.partials || p.ep) return false;
+  if (p.Cin % 32 || p.Cin < 64 || p.Cout % 64 || p.Di % KBD || p.Hi % KBH || p.Wi % KBW) return false;      // (>= 2 slabs: the deferred stores of a class ride in the next one's first item)
+  if (p.Do != 2 * p.Di || p.Ho != 2 * p.Hi || p.Wo != 2 * p.Wi) return false;
+  if (p.B > 255 || p.Di / KBD > 255 || p.Hi / KBH > 255 || p.Wi / KBW > 255) return false;
+  if ((size_t)(KED + 1) * p.Hi * p.Wi * p.Cin * 2 >= 0x7fffff00ull || (size_t)16 * p.Wo * p.Cout * 2 >= 0x7fffff00ull) return false;
+  return k3_units(p.B, p.Di, p.Hi, p.Wi, p.Cout) >= K3_MIN_UNITS;
+}
+
+// the kernel's arguments from the caller's: both instantiations walk the SOURCE grid (= the output grid of the k3 s1 launches)
+static void k3_fill(K3Args& a, const ConvProblem& p, const ConvArgs& c) {
   a.x = (const bf16_t*)c.x; a.w = (const bf16_t*)c.w; a.bias = c.bias; a.y = (bf16_t*)c.y; a.partials = c.partials;
   a.ep_scale = c.ep_scale; a.ep_shift = c.ep_shift; a.ep_res = (const bf16_t*)c.ep_res; a.ep_act = c.ep_act;
   a.B = c.B; a.D = c.Di; a.H = c.Hi; a.W = c.Wi; a.Cin = c.Cin; a.Cout = c.Cout; a.Cinp = c.Cinp; a.Coutp = c.Coutp;
-  a.nbd = c.Di / KBD; a.nbh = c.Hi / KBH; a.nbw = c.Wi / KBW; a.ny = k3_tiles(c.Cout); a.nunit = units; a.nslab = c.Cinp / 32;
-  a.flip = mode == AM_CONV_DGRAD;
+  a.nbd = c.Di / KBD; a.nbh = c.Hi / KBH; a.nbw = c.Wi / KBW; a.ny = k3_tiles(c.Cout); a.nunit = k3_units(c.B, c.Di, c.Hi, c.Wi, c.Cout); a.nslab = c.Cinp / 32;
+  a.flip = p.mode == AM_CONV_DGRAD;
   a.nt_store = (size_t)c.B * c.Do * c.Ho * c.Wo * c.Cout * 2 >= ((size_t)384 << 20);
   a.w_bytes = (unsigned)c.w_bytes;
 #ifdef AM_ABLATE
   { const char* e = getenv("AM_K3_DBG"); a.dbg = e ? atoi(e) : 0; }
 #endif
-  const bool ep = a.ep_scale || a.ep_res || a.ep_act != AM_ACT_NONE;
-  auto kern = ep ? conv_k3_kernel<4, true, false> : (a.partials ? conv_k3_kernel<4, false, true> : conv_k3_kernel<4, false, false>);
-  if (c.Cout % 64) kern = ep ? conv_k3_kernel<2, true, false> : (a.partials ? conv_k3_kernel<2, false, true> : conv_k3_kernel<2, false, false>);
-  else if (a.partials && !ep && c.stats_sum_only) kern = conv_k3_kernel<4, false, true, false, true>;      // (the rows' sum-of-squares column stays zero)
+}
+
+int conv_k3_launch(const ConvProblem& p, ConvArgs& c, const int*, void* stream, int* rows) {
+  if (!conv_k3_serves(p)) return 0;
+  const int dev = am_device();
+  K3Args a;
+  k3_fill(a, p, c);
+  const int G = k3_grid(a.nunit, c.Cout, dev);
+  auto kern = p.ep ? conv_k3_kernel<4, true, false> : (a.partials ? conv_k3_kernel<4, false, true> : conv_k3_kernel<4, false, false>);
+  if (c.Cout % 64) kern = p.ep ? conv_k3_kernel<2, true, false> : (a.partials ? conv_k3_kernel<2, false, true> : conv_k3_kernel<2, false, false>);
+  else if (a.partials && !p.ep && c.stats_sum_only) kern = conv_k3_kernel<4, false, true, false, true>;      // (the rows' sum-of-squares column stays zero)
   AM_HIP_STAGE((am_lds_optin<conv_k3_kernel<4, true, false>, conv_k3_kernel<4, false, true>, conv_k3_kernel<4, false, false>,
                              conv_k3_kernel<2, true, false>, conv_k3_kernel<2, false, true>, conv_k3_kernel<2, false, false>,
                              conv_k3_kernel<4, false, true, false, true>>(dev)));
@@ -641,29 +636,14 @@ int conv_k3_launch(int mode, int dtype, int ksize, int stride, ConvArgs& c, void
   return 1;
 }
 
-// ConvTranspose3d k4 s2 p1 (bf16, dense): 1 = served by the persistent kernel's transposed instantiation, 0 = does not qualify
-int conv_k3t_launch(int mode, int dtype, int ksize, int stride, ConvArgs& c, void* stream) {
-  if (!k3t_serves(mode, dtype, ksize, stride, c.B, c.Di, c.Hi, c.Wi, c.Do, c.Ho, c.Wo, c.Cin, c.Cout, c.in_mask.m || c.out_mask.m, c.accumulate != 0,
-                  c.nb_x != nullptr, c.ep_scale || c.ep_res || c.ep_act != AM_ACT_NONE, c.partials != nullptr)) return 0;
+int conv_k3t_launch(const ConvProblem& p, ConvArgs& c, const int*, void* stream, int*) {
+  if (!conv_k3t_serves(p)) return 0;
   const int dev = am_device();
-  const int units = k3_units(c.B, c.Di, c.Hi, c.Wi, c.Cout), G = k3_grid(units, c.Cout, dev);
-#ifdef AM_ABLATE
-  { const char* e_ = getenv("AM_CV_NOK3T"); if (e_ && atoi(e_)) return 0; }
-#endif
   K3Args a;
-  a.x = (const bf16_t*)c.x; a.w = (const bf16_t*)c.w; a.bias = c.bias; a.y = (bf16_t*)c.y; a.partials = nullptr;
-  a.ep_scale = nullptr; a.ep_shift = nullptr; a.ep_res = nullptr; a.ep_act = AM_ACT_NONE;
-  a.B = c.B; a.D = c.Di; a.H = c.Hi; a.W = c.Wi; a.Cin = c.Cin; a.Cout = c.Cout; a.Cinp = c.Cinp; a.Coutp = c.Coutp;
-  a.nbd = c.Di / KBD; a.nbh = c.Hi / KBH; a.nbw = c.Wi / KBW; a.ny = c.Cout / 64; a.nunit = units; a.nslab = c.Cinp / 32;
-  a.flip = 0;
-  a.nt_store = (size_t)c.B * c.Do * c.Ho * c.Wo * c.Cout * 2 >= ((size_t)384 << 20);
-  a.w_bytes = (unsigned)c.w_bytes;
-#ifdef AM_ABLATE
-  { const char* e = getenv("AM_K3_DBG"); a.dbg = e ? atoi(e) : 0; }
-#endif
+  k3_fill(a, p, c);                        // (no partials, no epilogue: conv_k3t_serves; Cout % 64 == 0: 64-channel tiles)
   constexpr auto kern = conv_k3_kernel<4, false, false, true>;
   AM_HIP_STAGE(am_lds_optin<kern>(dev));
-  AM_LAUNCH(kern, dim3(G), dim3(512), KLDS, (hipStream_t)stream, a);
+  AM_LAUNCH(kern, dim3(k3_grid(a.nunit, c.Cout, dev)), dim3(512), KLDS, (hipStream_t)stream, a);
   AM_CHECK_LAUNCH_STAGE();
   return 1;
 }

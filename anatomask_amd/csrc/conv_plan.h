@@ -1,5 +1,5 @@
 // Shared between the convolution kernels (conv_igemm.hip: generic gather implicit GEMM; conv_rw.hip: resident-weight variant
-// for thin layers): launch arguments, tap plan, LDS layouts.
+// for thin layers; conv_gather.hip; conv_k3.hip): launch arguments, tap plan, LDS layouts, and the kernel-selection stages.
 #pragma once
 #include "common.h"
 
@@ -55,6 +55,17 @@ __device__ __forceinline__ int swz(int row, int chunk) { return (row << 6) + ((c
 
 
 // host: tap tables ------------------------------------------------------------------------------
+// Shift u (voxels of the staged sub-lattice) of kernel tap t along one dimension; false: the tap is not of this parity's unit.  PLAIN: the source
+// voxel is q + (t - pad); FLIPPED (data gradient): q + (pad - t); SRC_PARITY: source voxel 2q + (t - pad) = 2(q + u) + r lies on the source
+// sub-lattice r == parity; OUT_PARITY: 2(q + u) = 2q + parity + pad - t, the tap is of the output parity class when that is even
+enum TapRule { TAP_PLAIN, TAP_FLIPPED, TAP_SRC_PARITY, TAP_OUT_PARITY };
+inline bool tap_shift(int rule, int t, int pad, int parity, int* u) {
+  if (rule == TAP_PLAIN) { *u = t - pad; return true; }
+  if (rule == TAP_FLIPPED) { *u = pad - t; return true; }
+  if (rule == TAP_SRC_PARITY) { const int sft = t - pad, r = ((sft % 2) + 2) % 2; *u = (sft - r) / 2; return r == parity; }
+  const int num = parity + pad - t; *u = num / 2; return !(num & 1);
+}
+
 struct Plan { ConvArgs a; int bd, bh, bw; size_t lds; int nit, nt_tile, tgs; };
 
 inline int build_plan(Plan& P, int mode, int k, int stride) {
@@ -69,6 +80,7 @@ inline int build_plan(Plan& P, int mode, int k, int stride) {
   if (a.OS == 2) a.nclass = 8;
   a.nunit = (a.OS == 2 || a.GS == 2) ? 8 : 1;
   if (k * k * k > 64) return -2;
+  const int rule = a.GS == 2 ? TAP_SRC_PARITY : mode == AM_CONV_FWD ? TAP_PLAIN : a.OS == 1 ? TAP_FLIPPED : TAP_OUT_PARITY;
   int n = 0;
   for (int c = 0; c < a.nunit; ++c) {
     a.tap_begin[c] = n;
@@ -79,15 +91,7 @@ inline int build_plan(Plan& P, int mode, int k, int stride) {
     for (int td = 0; td < k; ++td) for (int th = 0; th < k; ++th) for (int tw = 0; tw < k; ++tw) {
       const int t[3] = {td, th, tw};
       int u[3]; bool ok = true;
-      for (int d = 0; d < 3; ++d) {
-        if (a.GS == 2) {                       // source voxel 2q + (t - pad) = 2(q + u) + r: belongs to unit c iff r == p[d]
-          const int sft = t[d] - pad, r = ((sft % 2) + 2) % 2;
-          if (r != p[d]) { ok = false; break; }
-          u[d] = (sft - r) / 2;
-        } else if (mode == AM_CONV_FWD) u[d] = t[d] - pad;
-        else if (a.OS == 1) u[d] = pad - t[d];
-        else { const int num = p[d] + pad - t[d]; if (num & 1) { ok = false; break; } u[d] = num / 2; }
-      }
+      for (int d = 0; d < 3 && ok; ++d) ok = tap_shift(rule, t[d], pad, p[d], &u[d]);
       if (!ok) continue;
       if (n >= 64) return -2;
       a.taps[n++] = (u[0] + 8) | ((u[1] + 8) << 4) | ((u[2] + 8) << 8) | ((td * k * k + th * k + tw) << 12) | (c << 18);
@@ -124,25 +128,29 @@ inline int build_plan(Plan& P, int mode, int k, int stride) {
 }
 
 
-// resident-weight kernel (conv_rw.hip): returns 1 when it took the launch, 0 when the shape does not qualify, < 0 on error
-int conv_rw_launch(int mode, int dtype, int ksize, int stride, ConvArgs& a, const int* active_list, int n_active, void* stream);
-int conv_rw_rows(int mode, int dtype, int ksize, int stride, int B, int Do, int Ho, int Wo, int Cin, int Cout, int out_sparse, int out_bshift,
-                 int n_active);   // partial-sum rows such a launch writes, or 0 when the shape does not qualify
+// host: kernel selection -------------------------------------------------------------------------
+// Everything the choice of a kernel depends on, and nothing else: the entry points of conv_igemm.hip build one from their arguments
+// (am_conv3d_partials_rows and the other queries from the subset they are given) and every stage decides by it.
+struct ConvProblem {
+  int mode, dtype, ksize, stride, B, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout;
+  bool in_sparse, out_sparse, same_mask, has_list;   // in_mask / out_mask != NULL; they are one tensor; an active-patch list is given
+  int in_bshift, out_bshift, n_active, fd, fh, fw;
+  bool accumulate, ep, partials, sum_only;           // y +=; any of ep_scale / ep_res / ep_act; partials != NULL; AM_CONV_PARTIALS_SUM_ONLY
+  bool nbred, prenorm;                               // am_conv3d_nbred / am_conv3d_prenorm
+};
 
-// voxel-list gather kernel (conv_gather.hip): k3 s1 forward / data gradient of block-sparse tensors whose patches are at most 2^3 voxels
-int conv_gather_launch(int mode, int dtype, int ksize, int stride, ConvArgs& a, const int* active_list, int n_active, void* stream);
-int conv_gather_rows(int mode, int dtype, int ksize, int stride, int B, int Do, int Ho, int Wo, int Cin, int Cout, int out_sparse, int out_bshift,
-                     int n_active);   // partial-sum rows such a launch writes, or 0 when the shape does not qualify
-
-// dense k3 s1 forward / data gradient, bf16, persistent 8-wave LDS-DMA kernel (conv_k3.hip): 1 when it took the launch, 0 when the shape
-// does not qualify; conv_k3_rows = the partial-sum rows such a launch writes on the current device (8 per workgroup), or 0 -- a launch
-// that was served leaves the same number in *rows
-int conv_k3_launch(int mode, int dtype, int ksize, int stride, ConvArgs& a, void* stream, int* rows);
-int conv_k3_rows(int mode, int dtype, int ksize, int stride, int B, int D, int H, int W, int Cin, int Cout, int masks);
-int conv_k3t_launch(int mode, int dtype, int ksize, int stride, ConvArgs& c, void* stream);   // ConvTranspose3d k4 s2 p1 on the same kernel
-// which of the two serves an am_conv3d launch of this shape and these options (0 neither, 1 conv_k3_kernel, 2 its transposed instantiation):
-// the launchers' own predicates
-int conv_k3_which(int mode, int dtype, int ksize, int stride, int B, int Di, int Hi, int Wi, int Do, int Ho, int Wo, int Cin, int Cout,
-                  int masks, int accumulate, int ep, int partials);
+// One kernel family.  am_conv3d walks conv_stages (conv_igemm.hip) in order and the first stage that serves takes the launch.
+struct ConvStage {
+  const char* name;
+  int (*fits)(const ConvProblem&);      // shape-only acceptance (what am_conv3d_partials_rows knows: no source grid, no options): the partial-sum rows such a launch writes on the current device, or 0
+  bool (*serves)(const ConvProblem&);   // fits + every option condition: the stage takes exactly these launches
+  // 1 = served (*rows = what fits returns), 0 = !serves(p), < 0 = failed (AM_STAGE_ERR); `a` holds the caller's arguments, a stage adds its kernel's own
+  int (*launch)(const ConvProblem&, ConvArgs& a, const int* active_list, void* stream, int* rows);
+};
+#define AM_CONV_STAGE(name_) int name_##_fits(const ConvProblem&); bool name_##_serves(const ConvProblem&); \
+                             int name_##_launch(const ConvProblem&, ConvArgs&, const int*, void*, int*)
+AM_CONV_STAGE(conv_k3t); AM_CONV_STAGE(conv_k3);   // conv_k3.hip: dense bf16 ConvTranspose3d k4 s2 / k3 s1, persistent 8-wave LDS-DMA kernel
+AM_CONV_STAGE(conv_rw); AM_CONV_STAGE(conv_gather);   // conv_rw.hip: thin layers, all weights resident in LDS; conv_gather.hip: voxel-list gather (patches of at most 4^3 voxels, badly padded dense grids)
+AM_CONV_STAGE(conv_igemm);                         // conv_igemm.hip: the generic kernel, and the table `conv_stages` of all five
 
 }  // namespace amconv

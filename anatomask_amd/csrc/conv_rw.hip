@@ -405,8 +405,9 @@ _Pragma("unroll") \
 // which shapes qualify, and with what geometry
 struct RwGeo { int nw, bd, bh, bw, nt_tile, nwg, nbrick, pbd, pbh, pbw, pq; bool hr; };
 
-bool rw_geometry(RwGeo& G, int mode, int dtype, int k, int stride, int B, int Do, int Ho, int Wo, int Cin, int Cout, bool sparse, int out_bshift,
-                 int n_active) {
+bool rw_geometry(RwGeo& G, const ConvProblem& p) {
+  const int mode = p.mode, dtype = p.dtype, k = p.ksize, stride = p.stride, B = p.B, Do = p.Do, Ho = p.Ho, Wo = p.Wo, Cin = p.Cin, Cout = p.Cout;
+  const int out_bshift = p.out_bshift, n_active = p.n_active; const bool sparse = p.out_sparse;
   if (dtype != AM_DT_BF16 || k != 3 || Cin > 32 || Cin % 8 || Cout > 64 || Cout % 8) return false;
   const bool s1 = stride == 1 && (mode == AM_CONV_FWD || mode == AM_CONV_DGRAD);
   const bool s2 = stride == 2 && mode == AM_CONV_FWD;
@@ -450,19 +451,17 @@ int rw_launch(ConvArgs& a, RwArgs& r, const RwGeo& G, size_t lds, hipStream_t st
 
 // EVERY acceptance condition of the resident-weight kernel that follows from the shape alone: the geometry, the tap plan (h-run order for
 // the 8x4x16 brick), the LDS footprint (brick + all taps' weights + the workgroup's brick table, which grows with n_active: level 0 of
-// STUNet-B 128^3 stops fitting above ~4864 active patches) and the staging iteration count.  conv_rw_rows and am_conv3d_prenorm_supported
-// PREDICT with it what conv_rw_launch will do, so they cannot disagree with the launch.  P.a must hold the caller's arguments (or be default).
+// STUNet-B 128^3 stops fitting above ~4864 active patches) and the staging iteration count.  The stage's fits (am_conv3d_partials_rows,
+// am_conv3d_prenorm_supported) and its launch both evaluate it, so they cannot disagree.  P.a must hold the caller's arguments (or be default).
 struct RwFit { size_t lds; int ntaps; };
 constexpr int RW_LR = 96;                                // conflict-free AND additive row stride (the generic kernel's 80 B is 2-way conflicted: it must fit two workgroups per CU)
 
-static int rw_fit(RwGeo& G, Plan& P, RwFit& F, int mode, int dtype, int ksize, int stride, int B, int Do, int Ho, int Wo, int Cin, int Cout,
-                  bool sparse, int out_bshift, int n_active) {
-  if (!rw_geometry(G, mode, dtype, ksize, stride, B, Do, Ho, Wo, Cin, Cout, sparse, out_bshift, n_active)) return 0;
+static bool rw_fit(RwGeo& G, Plan& P, RwFit& F, const ConvProblem& p) {
+  if (!rw_geometry(G, p)) return false;
   P.bd = G.bd; P.bh = G.bh; P.bw = G.bw; P.nt_tile = G.nt_tile;
-  const int rc = build_plan(P, mode, ksize, stride);
-  if (rc) return rc;
+  if (build_plan(P, p.mode, p.ksize, p.stride)) return false;     // (k3, stride 1 / 2: every plan exists)
   ConvArgs& a = P.a;
-  if (G.hr && !a.hreuse) return 0;
+  if (G.hr && !a.hreuse) return false;
   F.ntaps = a.tap_begin[a.nunit];
   size_t mxv = 0;
   for (int c = 0; c < a.nunit; ++c) { const size_t v = (size_t)a.ed[c] * a.eh[c] * a.ew[c]; if (v > mxv) mxv = v; }
@@ -471,42 +470,46 @@ static int rw_fit(RwGeo& G, Plan& P, RwFit& F, int mode, int dtype, int ksize, i
   a.w_lds_off = (int)brick;
   const int chunk = (G.nbrick + G.nwg - 1) / G.nwg;      // bricks per workgroup -> 32-byte rows of its brick table
   F.lds = brick + (size_t)F.ntaps * G.nt_tile * ROWB + (size_t)chunk * 32;
-  if (F.lds > 160 * 1024) return 0;
+  if (F.lds > 160 * 1024) return false;
   const int nit = (int)((mxv * 4 + G.nw * 64 - 1) / (G.nw * 64));
   // 8x4x16 brick, haloed 10x6x18 = 1080 rows -> 9 staging iterations of 128 rows; 4x8x8 brick, sub-lattice sub-bricks of <= 5x9x9 = 405 rows -> 7 of 64
-  if (nit > (G.hr ? 9 : 7)) return 0;
-  return 1;
+  return nit <= (G.hr ? 9 : 7);
 }
 
 }  // namespace
 
 namespace amconv {
 
-int conv_rw_rows(int mode, int dtype, int ksize, int stride, int B, int Do, int Ho, int Wo, int Cin, int Cout, int out_sparse, int out_bshift,
-                 int n_active) {
+int conv_rw_fits(const ConvProblem& p) {
   RwGeo G; Plan P; RwFit F;
-  return rw_fit(G, P, F, mode, dtype, ksize, stride, B, Do, Ho, Wo, Cin, Cout, out_sparse != 0, out_bshift, n_active) == 1 ? G.nwg : 0;
+  return rw_fit(G, P, F, p) ? G.nwg : 0;
 }
 
-int conv_rw_launch(int mode, int dtype, int ksize, int stride, ConvArgs& a0, const int* active_list, int n_active, void* stream) {
-  const bool sparse = a0.out_mask.m != nullptr;
-  if (sparse != (a0.in_mask.m != nullptr) || (sparse && a0.in_mask.m != a0.out_mask.m)) return 0;
-  if (a0.accumulate || a0.ep_scale || a0.ep_res || a0.ep_act != AM_ACT_NONE) return 0;
-  if (sparse && !active_list) return 0;
-  if (a0.in_scale && (!a0.in_shift || mode != AM_CONV_FWD)) return 0;
-  if (sparse) {                                          // the source halo must stay inside the 3x3x3 patch neighbourhood
-    const int in_patch = 1 << a0.in_mask.bs;
-    if (in_patch < 4 || (in_patch != (1 << a0.out_mask.bs) * (mode == AM_CONV_FWD ? stride : 1))) return 0;
+bool conv_rw_serves(const ConvProblem& p) {
+#ifdef AM_ABLATE
+  if (getenv("AM_CV_NORW")) return false;
+#endif
+  if (p.nbred || p.accumulate || p.ep) return false;     // (the fused reduce lives in conv_igemm_kernel only)
+  if (p.out_sparse != p.in_sparse || (p.out_sparse && (!p.same_mask || !p.has_list))) return false;
+  if (p.prenorm && p.mode != AM_CONV_FWD) return false;
+  if (p.out_sparse) {                                    // the source halo must stay inside the 3x3x3 patch neighbourhood
+    const int in_patch = 1 << p.in_bshift;
+    if (in_patch < 4 || (in_patch != (1 << p.out_bshift) * (p.mode == AM_CONV_FWD ? p.stride : 1))) return false;
   }
+  return conv_rw_fits(p) > 0;
+}
+
+int conv_rw_launch(const ConvProblem& p, ConvArgs& a0, const int* active_list, void* stream, int* rows) {
+  if (!conv_rw_serves(p)) return 0;
   RwGeo G; Plan P; RwFit F;
   P.a = a0;
-  const int fit = rw_fit(G, P, F, mode, dtype, ksize, stride, a0.B, a0.Do, a0.Ho, a0.Wo, a0.Cin, a0.Cout, sparse, a0.out_mask.bs, n_active);
-  if (fit != 1) return fit;
+  rw_fit(G, P, F, p);
   ConvArgs& a = P.a;
   a.nbd = a.Do / G.bd; a.nbh = a.Ho / G.bh; a.nbw = a.Wo / G.bw;
   RwArgs r;
-  r.plist = sparse ? active_list : nullptr; r.nbrick = G.nbrick; r.pbd = G.pbd; r.pbh = G.pbh; r.pbw = G.pbw; r.pq = G.pq; r.ntaps = F.ntaps;
+  r.plist = p.out_sparse ? active_list : nullptr; r.nbrick = G.nbrick; r.pbd = G.pbd; r.pbh = G.pbh; r.pbw = G.pbw; r.pq = G.pq; r.ntaps = F.ntaps;
   hipStream_t st = (hipStream_t)stream;
+  if (rows) *rows = G.nwg;
   if (G.hr) return rw_launch<8, 8, 4, 16, 2, 9, true, RW_LR>(a, r, G, F.lds, st);
   return G.nt_tile == 32 ? rw_launch<4, 4, 8, 8, 2, 7, false, RW_LR>(a, r, G, F.lds, st) : rw_launch<4, 4, 8, 8, 4, 7, false, RW_LR>(a, r, G, F.lds, st);
 }

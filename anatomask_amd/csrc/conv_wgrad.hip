@@ -23,6 +23,7 @@
 #include <stdlib.h>
 #include "common.h"
 #include "../../include/anatomask_hip.h"
+#include "conv_plan.h"
 
 namespace amconv {
 // conv_wgk3.hip: dense bf16 k3 s1 weight gradients with 64 x 64 channel tiles on the 8-wave LDS-DMA kernel; 1 = served, 0 = does not qualify
@@ -834,7 +835,7 @@ __global__ __launch_bounds__(256) void wg_gemm_nt_kernel(const bf16_t* __restric
 
 // the gather form applies: bf16, conv k3 (stride 1 or 2), block-sparse dY with 1- or 2-voxel patches and an active-patch list, channel
 // counts that tile by 128 x 64
-inline bool wg_gather_ok(int mode, int dtype, int k, int stride, int Cx, int Cy, const uint8_t* y_mask, int y_bshift, const int32_t* list,
+inline bool wg_gather_ok(int mode, int dtype, int k, int stride, int Cx, int Cy, bool y_mask, int y_bshift, bool list,
                          int n_active, int B, int fd, int fh, int fw) {
   // where it was measured ahead of the brick kernel (profiles/r04_experiments.md): one-voxel patches, and the strided layers into 2-voxel patches from
   // 256 input channels on (the brick kernel stages 8 parity sub-lattices there).  Its GEMM is bound by L2 bandwidth at ~160 TFLOP/s (128 x 64
@@ -842,6 +843,13 @@ inline bool wg_gather_ok(int mode, int dtype, int k, int stride, int Cx, int Cy,
   if (!(y_bshift == 0 || (y_bshift == 1 && stride == 2 && Cx >= 256))) return false;
   return mode == AM_CONV_FWD && dtype == AM_DT_BF16 && k == 3 && (stride == 1 || stride == 2) && y_mask && list && n_active > 0 &&
          Cy % 128 == 0 && Cx % 64 == 0 && B <= 255 && fd <= 255 && fh <= 255 && fw <= 255;
+}
+
+// the launch goes to the 8-wave LDS-DMA kernel of conv_wgk3.hip: the one predicate of am_conv3d_wgrad and am_conv3d_wgrad_uses_k3
+inline bool wgk3_serves(int mode, int dtype, int k, int stride, int B, int Dx, int Hx, int Wx, int Cx, int Dy, int Hy, int Wy, int Cy,
+                        bool masks, bool deterministic) {
+  return dtype == AM_DT_BF16 && mode == AM_CONV_FWD && k == 3 && stride == 1 && !masks && !deterministic && Dx == Dy && Hx == Hy && Wx == Wy &&
+         amconv::conv_wgk3_qualifies(B, Dy, Hy, Wy, Cx, Cy);
 }
 
 }  // namespace
@@ -863,7 +871,7 @@ extern "C" int am_conv3d_wgrad(int mode, int dtype, int ksize, int stride, const
   a.y_mask = MaskView{y_mask, fd, fh, fw, y_bshift};
   const int* const plist0 = (y_mask && active_list && n_active > 0) ? active_list : nullptr;
   const int k = ksize;
-  if (gather_workspace && wg_gather_ok(mode, dtype, ksize, stride, Cx, Cy, y_mask, y_bshift, active_list, n_active, B, fd, fh, fw)) {
+  if (gather_workspace && wg_gather_ok(mode, dtype, ksize, stride, Cx, Cy, y_mask != nullptr, y_bshift, active_list != nullptr, n_active, B, fd, fh, fw)) {
     WgGather ga;
     ga.x = (const bf16_t*)x; ga.dy = (const bf16_t*)dy;
     ga.B = B; ga.Dx = Dx; ga.Hx = Hx; ga.Wx = Wx; ga.Cx = Cx; ga.Dy = Dy; ga.Hy = Hy; ga.Wy = Wy; ga.Cy = Cy;
@@ -896,7 +904,7 @@ extern "C" int am_conv3d_wgrad(int mode, int dtype, int ksize, int stride, const
   { const char* e_ = getenv("AM_WG_DBG"); a.dbg = e_ ? atoi(e_) : 0; }
 #endif
   const bool bf = dtype == AM_DT_BF16;
-  if (bf && mode == AM_CONV_FWD && ksize == 3 && stride == 1 && !x_mask && !y_mask && !det_workspace && Dx == Dy && Hx == Hy && Wx == Wy) {
+  if (wgk3_serves(mode, dtype, ksize, stride, B, Dx, Hx, Wx, Cx, Dy, Hy, Wy, Cy, x_mask || y_mask, det_workspace != nullptr)) {
     const int rc = amconv::conv_wgk3_launch(x, dy, dw_packed, B, Dy, Hy, Wy, Cx, Cy, stream);
     if (rc < 0) return rc;                                 // (a failed launch: never "served", never a silent fall-through)
     if (rc == 1) return 0;
@@ -961,6 +969,8 @@ extern "C" int am_conv3d_wgrad(int mode, int dtype, int ksize, int stride, const
     if (mi == 2 && nwx == 2) bd = 4;                     // thin rows: a 256-voxel brick still fits two workgroups per CU
   }
   const int pad = (mode == AM_CONVT_FWD) ? 1 : k / 2;
+  // (plain for S2 too: shifts in full-resolution voxels around 2q)
+  const int rule = mode == AM_CONVT_FWD ? amconv::TAP_OUT_PARITY : a.GS == 2 ? amconv::TAP_SRC_PARITY : amconv::TAP_PLAIN;
   int n = 0; size_t maxvox = 0;
   int ucount[8];
   for (int gI = 0; gI < nunit; ++gI) {
@@ -972,11 +982,7 @@ extern "C" int am_conv3d_wgrad(int mode, int dtype, int ksize, int stride, const
     for (int td = 0; td < k; ++td) for (int th = 0; th < k; ++th) for (int tw = 0; tw < k; ++tw) {
       const int t[3] = {td, th, tw};
       int u[3]; bool ok = true;
-      for (int d = 0; d < 3 && ok; ++d) {
-        if (mode == AM_CONVT_FWD) { const int num = p[d] + pad - t[d]; if (num & 1) ok = false; else u[d] = num / 2; }
-        else if (a.GS == 2) { const int sft = t[d] - pad, r = ((sft % 2) + 2) % 2; if (r != p[d]) ok = false; else u[d] = (sft - r) / 2; }
-        else u[d] = t[d] - pad;                           // (S2: shifts in full-resolution voxels around 2q)
-      }
+      for (int d = 0; d < 3 && ok; ++d) ok = amconv::tap_shift(rule, t[d], pad, p[d], &u[d]);
       if (ok && mode == AM_CONV_FWD && a.GS == 1 && td != gI) ok = false;
       if (!ok) continue;
       a.taps[n++] = (u[0] + 8) | ((u[1] + 8) << 4) | ((u[2] + 8) << 8) | ((td * k * k + th * k + tw) << 12);
@@ -1056,16 +1062,14 @@ extern "C" int am_conv3d_wgrad(int mode, int dtype, int ksize, int stride, const
 
 extern "C" int am_conv3d_wgrad_uses_k3(int mode, int dtype, int ksize, int stride, int B, int D, int H, int W, int Cx, int Cy, int has_masks,
                                        int deterministic) {
-  return (dtype == AM_DT_BF16 && mode == AM_CONV_FWD && ksize == 3 && stride == 1 && !has_masks && !deterministic &&
-          amconv::conv_wgk3_qualifies(B, D, H, W, Cx, Cy)) ? 1 : 0;
+  return wgk3_serves(mode, dtype, ksize, stride, B, D, H, W, Cx, D, H, W, Cy, has_masks != 0, deterministic != 0) ? 1 : 0;
 }
 
 extern "C" int am_conv3d_wgrad_gather_bytes(int mode, int dtype, int ksize, int stride, int B, int Cx, int Cy, int y_bshift, int has_y_mask, int n_active,
                                             int fd, int fh, int fw, long* bytes) {
-  static const uint8_t one = 1; static const int32_t lst = 0;
   if (!bytes) return -1;
   *bytes = 0;
-  if (!wg_gather_ok(mode, dtype, ksize, stride, Cx, Cy, has_y_mask ? &one : nullptr, y_bshift, &lst, n_active, B, fd, fh, fw)) return 0;
+  if (!wg_gather_ok(mode, dtype, ksize, stride, Cx, Cy, has_y_mask != 0, y_bshift, true, n_active, B, fd, fh, fw)) return 0;
   const long pq3 = 1L << (3 * y_bshift), Np = ((long)n_active * pq3 + 31) / 32 * 32;
   const long ntaps = (long)ksize * ksize * ksize, all = 2 * Np * (Cy + ntaps * Cx), third = 2 * Np * (Cy + (ntaps / 3) * Cx);
   *bytes = all <= (640L << 20) ? all : third;            // all 27 taps in one round when that stays under 640 MB, else three rounds of 9

@@ -1510,3 +1510,61 @@ def test_row_walk_kernels_beyond_the_linear_decode_limit(ops):
     assert err <= 2e-2 * want.abs().max().item(), err
     with pytest.raises(RuntimeError, match="am_chan_sum failed with code -4"):      # a linear-walk kernel still refuses
         ops.chan_sum(x, mi, 4, torch.zeros(C, device=DEV))
+
+
+# one case per stage of the kernel-selection table (conv_igemm.hip conv_stages), each at the smallest shape the stage's own predicate
+# accepts: (stage, mode, dtype, cin, cout, k, stride, B, source grid, patch grid f, block shift, active patches per sample)
+STAGE_CASES = [
+    ("conv_k3", "fwd", torch.bfloat16, 64, 64, 3, 1, 4, (32, 32, 32), None, 0, 0),       # 256 units of 8x4x16 voxels x 64 channels
+    ("conv_k3t", "convt", torch.bfloat16, 64, 64, 4, 2, 4, (32, 32, 32), None, 0, 0),    # 32^3 -> 64^3, 256 units
+    ("conv_rw", "fwd", torch.bfloat16, 32, 32, 3, 1, 1, (32, 32, 32), (2, 2, 2), 4, 4),   # 16-voxel patches, half of the 8 active
+    ("conv_gather", "fwd", torch.bfloat16, 128, 128, 3, 1, 1, (8, 8, 8), (4, 4, 4), 1, 33),   # 2-voxel patches: 264 active voxels, a ragged third tile
+    ("conv_igemm", "fwd", torch.float32, 16, 24, 3, 1, 1, (8, 12, 16), None, 0, 0),
+]
+
+
+@pytest.mark.parametrize("case", STAGE_CASES, ids=[c[0] for c in STAGE_CASES])
+def test_conv_stage_launch_agrees_with_its_own_row_count(ops, case):
+    """Every stage of the selection table serves a launch: the output against F.conv3d / F.conv_transpose3d (then the mask) at this file's
+    tolerances, the partial rows the launch reports <= am_conv3d_partials_rows, and == the stage's own count -- 8 per workgroup and one
+    workgroup per CU (conv_k3), min(256 / channel slices, live bricks) (conv_rw), ceil(active voxels / 128) x classes (conv_gather),
+    live bricks x classes (conv_igemm) -- which no other stage would report for the shape.  conv_k3t writes no rows: am_conv3d_uses_k3 == 2."""
+    import ctypes
+    from anatomask_amd import hip
+    stage, mode, dtype, cin, cout, k, stride, B, si, f, bs, keep = case
+    so = tuple(2 * v for v in si) if mode == "convt" else si
+    x = q(rnd(B, cin, *si, seed=81), dtype)
+    bias = rnd(cout, seed=83)
+    if mode == "convt":
+        w = q(rnd(cin, cout, 4, 4, 4, seed=82, scale=1.0 / np.sqrt(cin * 8)), dtype)
+        yr = F.conv_transpose3d(x, w, bias, stride=2, padding=1)
+    else:
+        w = q(rnd(cout, cin, 3, 3, 3, seed=82, scale=1.0 / np.sqrt(cin * 27)), dtype)
+        yr = F.conv3d(x, w, bias, padding=1)
+    mi = mo = None
+    xd = to_cl(x, dtype)
+    if f is not None:
+        mask = mk_mask(B, f, keep, seed=7)
+        mi = ops.MaskInfo.from_bool(mask, DEV)
+        mo = O.upsample_mask(mask, so).float()
+        yr = F.conv3d(x * mo, w, bias, padding=1) * mo
+        xd = torch.where(to_cl(mo.expand_as(x), dtype) > 0, xd, torch.full_like(xd, float("nan")))      # inactive voxels may hold anything
+    code = hip.DT_BF16 if dtype == torch.bfloat16 else hip.DT_F32
+    opmode = ops.CONVT_FWD if mode == "convt" else ops.CONV_FWD
+    uses = hip.lib()._lib.am_conv3d_uses_k3(opmode, code, k, stride, B, *si, cin, *so, cout, int(f is not None), 0, 0, int(stage != "conv_k3t"))
+    assert uses == {"conv_k3": 1, "conv_k3t": 2}.get(stage, 0)
+    wp = ops.pack_weight(w.to(DEV), dtype, mode == "convt", False)
+    if stage == "conv_k3t":
+        y = ops.conv3d(opmode, xd, wp, bias.to(DEV), so, k, stride)
+        close(from_cl(y), yr, TOL[dtype], stage)
+        return
+    y, part = ops.conv3d(opmode, xd, wp, bias.to(DEV), so, k, stride, in_mask=mi, in_bshift=bs, out_mask=mi, out_bshift=bs, want_partials=True)
+    close(from_cl(y), yr, TOL[dtype], stage, mo)
+    bound = ctypes.c_int(0)
+    hip.lib().conv3d_partials_rows(opmode, code, k, stride, B, *so, cin, cout, int(f is not None), bs, B * keep, ctypes.addressof(bound))
+    own = {"conv_k3": 8 * torch.cuda.get_device_properties(0).multi_processor_count,      # (256 units >= the CUs; one channel tile)
+           "conv_rw": min(256 // 1, B * keep * (16 // 8) * (16 // 4) * (16 // 16)),        # 8x4x16 bricks of the active 16^3 patches, one 32-channel slice
+           "conv_gather": -(-B * keep * 8 // 128) * 1,                                     # 2^3 voxels per patch, one class (stride 1)
+           "conv_igemm": B * 2 * 3 * 4}[stage]                                             # 4x4x4 bricks of the 8 x 12 x 16 grid (tiny grids), one class
+    assert part.rows <= bound.value, (part.rows, bound.value)
+    assert part.rows == own, (stage, part.rows, own)
