@@ -43,6 +43,46 @@ template <typename T> struct Walk {
   }
 };
 
+// ---- lane fold: the epilogue of every reduction below, linear or row walk (thread t owns channel chunk t % cpv in both) --------
+// Every thread of the workgroup leaves its NS x EPC partial sums in red[(t * NS + k) * 8 + i] (idle threads: zeros); after ONE
+// barrier thread t < cpv adds the nlane = blockDim.x / cpv lanes of its chunk in ascending order into a[k][i] (A: double, or float
+// where the sum goes on as fp32).  Returns whether the calling thread holds a result.  The caller passes nlane: the linear kernels
+// hold it as Walk::vpp already (NT / cpv with NT == blockDim.x), the row-walk kernels divide.
+template <int NS, typename A, int EPC>
+__device__ __forceinline__ bool lane_fold(float* red, int cpv, int nlane, const float (&s)[NS][EPC], A (&a)[NS][EPC]) {
+#pragma unroll
+  for (int k = 0; k < NS; ++k)
+#pragma unroll
+    for (int i = 0; i < EPC; ++i) red[(threadIdx.x * NS + k) * 8 + i] = s[k][i];
+  __syncthreads();
+  if (threadIdx.x >= cpv) return false;
+#pragma unroll
+  for (int k = 0; k < NS; ++k)
+#pragma unroll
+    for (int i = 0; i < EPC; ++i) a[k][i] = (A)0;
+  for (int vl = 0; vl < nlane; ++vl) {
+    const int t = vl * cpv + threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < NS; ++k)
+#pragma unroll
+      for (int i = 0; i < EPC; ++i) a[k][i] += red[(t * NS + k) * 8 + i];
+  }
+  return true;
+}
+
+// statistics [NREP][C][2]: one double atomic per workgroup, channel and column
+template <int EPC>
+__device__ __forceinline__ void flush_stats(float* red, int cpv, int nlane, int C, const float (&s)[2][EPC], double* sums) {
+  double a[2][EPC];
+  if (!lane_fold(red, cpv, nlane, s, a)) return;
+  double* sr = sums + (size_t)(blockIdx.x % NREP) * C * 2;
+#pragma unroll
+  for (int i = 0; i < EPC; ++i) {
+    const int c = threadIdx.x * EPC + i;
+    atomicAdd(&sr[c * 2], a[0][i]); atomicAdd(&sr[c * 2 + 1], a[1][i]);
+  }
+}
+
 // ------------------------------------------------------------------ statistics (forward)
 // sums[c][0] += sum x, sums[c][1] += sum x^2 over active voxels (double atomics, one per WG per channel)
 template <typename T, int NT = 256>
@@ -50,9 +90,9 @@ __global__ __launch_bounds__(NT) void chan_stats_kernel(const T* __restrict__ x,
   constexpr int EPC = TT<T>::EPC;
   __shared__ float red[NT * 2 * 8];
   Walk<T> wk(g.C, NT);
-  float s1[EPC], s2[EPC];
+  float s[2][EPC];
 #pragma unroll
-  for (int i = 0; i < EPC; ++i) s1[i] = s2[i] = 0.f;
+  for (int i = 0; i < EPC; ++i) s[0][i] = s[1][i] = 0.f;
   const long v0 = (long)blockIdx.x * g.vpw, v1 = min(v0 + (long)g.vpw, g.nvox());
   if (wk.live)
     for (long v = v0 + wk.vl; v < v1; v += wk.vpp) {
@@ -60,27 +100,9 @@ __global__ __launch_bounds__(NT) void chan_stats_kernel(const T* __restrict__ x,
       float f[EPC];
       chunk_to_f<T>(*(const u32x4*)(x + v * g.C + wk.cl * EPC), f);
 #pragma unroll
-      for (int i = 0; i < EPC; ++i) { s1[i] += f[i]; s2[i] += f[i] * f[i]; }
+      for (int i = 0; i < EPC; ++i) { s[0][i] += f[i]; s[1][i] += f[i] * f[i]; }
     }
-#pragma unroll
-  for (int i = 0; i < EPC; ++i) { red[(threadIdx.x * 2) * 8 + i] = s1[i]; red[(threadIdx.x * 2 + 1) * 8 + i] = s2[i]; }
-  __syncthreads();
-  if (threadIdx.x < wk.cpv) {                      // one thread per chunk lane folds the voxel lanes
-    double a1[EPC], a2[EPC];
-#pragma unroll
-    for (int i = 0; i < EPC; ++i) a1[i] = a2[i] = 0.0;
-    for (int vl = 0; vl < wk.vpp; ++vl) {
-      const int t = vl * wk.cpv + threadIdx.x;
-#pragma unroll
-      for (int i = 0; i < EPC; ++i) { a1[i] += red[(t * 2) * 8 + i]; a2[i] += red[(t * 2 + 1) * 8 + i]; }
-    }
-#pragma unroll
-    for (int i = 0; i < EPC; ++i) {
-      const int c = threadIdx.x * EPC + i;
-      double* sr = sums + (size_t)(blockIdx.x % NREP) * g.C * 2;
-      atomicAdd(&sr[c * 2], a1[i]); atomicAdd(&sr[c * 2 + 1], a2[i]);
-    }
-  }
+  flush_stats(red, wk.cpv, wk.vpp, g.C, s, sums);
 }
 
 // count of active voxels implied by the mask (dense: B*D*H*W)
@@ -94,15 +116,11 @@ __global__ void mask_count_kernel(const uint8_t* mask, int n, int voxels_per_pat
   if (threadIdx.x == 0) out[0] = (part[0] + part[1] + part[2] + part[3]) * voxels_per_patch;
 }
 
-// mean / rstd / folded scale+shift; optional BatchNorm running-stat update (momentum, unbiased var)
-__global__ void norm_finalize_kernel(const double* sums, int nrep, const double* count_ptr, double count_host, int C,
-                                     const float* gamma, const float* beta, float eps, float* mean, float* rstd,
-                                     float* scale, float* shift, float* run_mean, float* run_var, float momentum) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= C) return;
-  const double n = count_ptr ? count_ptr[0] : count_host;
-  double q1 = 0.0, q2 = 0.0;
-  for (int r = 0; r < nrep; ++r) { q1 += sums[((size_t)r * C + c) * 2]; q2 += sums[((size_t)r * C + c) * 2 + 1]; }
+// channel c: (q1, q2) = (sum x, sum x^2) over n voxels -> mean / rstd / folded scale+shift; optional BatchNorm running-stat update
+// (momentum, unbiased var)
+__device__ __forceinline__ void norm_coeffs(int c, double q1, double q2, double n, const float* gamma, const float* beta, float eps,
+                                            float* mean, float* rstd, float* scale, float* shift, float* run_mean, float* run_var,
+                                            float momentum) {
   const double m = q1 / n;
   double var = q2 / n - m * m;
   if (var < 0) var = 0;
@@ -114,6 +132,17 @@ __global__ void norm_finalize_kernel(const double* sums, int nrep, const double*
     run_mean[c] = (1.f - momentum) * run_mean[c] + momentum * (float)m;
     run_var[c] = (1.f - momentum) * run_var[c] + momentum * (float)(var * (n / (n - 1.0)));
   }
+}
+
+__global__ void norm_finalize_kernel(const double* sums, int nrep, const double* count_ptr, double count_host, int C,
+                                     const float* gamma, const float* beta, float eps, float* mean, float* rstd,
+                                     float* scale, float* shift, float* run_mean, float* run_var, float momentum) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= C) return;
+  const double n = count_ptr ? count_ptr[0] : count_host;
+  double q1 = 0.0, q2 = 0.0;
+  for (int r = 0; r < nrep; ++r) { q1 += sums[((size_t)r * C + c) * 2]; q2 += sums[((size_t)r * C + c) * 2 + 1]; }
+  norm_coeffs(c, q1, q2, n, gamma, beta, eps, mean, rstd, scale, shift, run_mean, run_var, momentum);
 }
 
 // eval-mode BatchNorm: fold running stats
@@ -214,7 +243,18 @@ __device__ __forceinline__ bool last_workgroup(unsigned* ticket) {
   return tk == gridDim.x - 1;
 }
 
-// bsum [NREP][C][3] -> k0/k1/k2 + parameter gradients (norm_bwd_finalize_kernel's arithmetic), accumulators re-zeroed
+// channel c: (b1, b2) = (sum dpre, sum dpre*xhat) over n voxels -> the coefficients of the apply pass (dx = k0*dpre - k1 - k2*xhat)
+// + the affine gradients, accumulated into fp32 grads (dbeta2: bias of a conv added AFTER the norm, the 1x1 shortcut: same sum)
+__device__ __forceinline__ void norm_bwd_coeffs(int c, double b1, double b2, double n, const float* gamma, const float* rstd,
+                                                float* k0, float* k1, float* k2, float* dgamma, float* dbeta, float* dbeta2) {
+  const float gr = gamma[c] * rstd[c];
+  k0[c] = gr; k1[c] = gr * (float)(b1 / n); k2[c] = gr * (float)(b2 / n);
+  if (dgamma) dgamma[c] += (float)b2;
+  if (dbeta) dbeta[c] += (float)b1;
+  if (dbeta2) dbeta2[c] += (float)b1;
+}
+
+// bsum [NREP][C][3] -> k0/k1/k2 + parameter gradients (what norm_bwd_finalize_kernel does), accumulators re-zeroed
 __device__ __forceinline__ void bwd_reduce_tail(double* bsum, int C, const BwdFin& f) {
   if (!f.ticket) return;
   if (!last_workgroup(f.ticket)) return;
@@ -227,11 +267,7 @@ __device__ __forceinline__ void bwd_reduce_tail(double* bsum, int C, const BwdFi
       b2 += __longlong_as_double(atomicExch((unsigned long long*)&q[1], 0ull));
       b3 += __longlong_as_double(atomicExch((unsigned long long*)&q[2], 0ull));
     }
-    const float gr = f.gamma[c] * f.rstd[c];
-    f.k0[c] = gr; f.k1[c] = gr * (float)(b1 / n); f.k2[c] = gr * (float)(b2 / n);
-    if (f.dgamma) f.dgamma[c] += (float)b2;
-    if (f.dbeta) f.dbeta[c] += (float)b1;
-    if (f.dbeta2) f.dbeta2[c] += (float)b1;
+    norm_bwd_coeffs(c, b1, b2, n, f.gamma, f.rstd, f.k0, f.k1, f.k2, f.dgamma, f.dbeta, f.dbeta2);
     if (f.dtoken) f.dtoken[c] += (float)b3;
   }
   if (threadIdx.x == 0) atomicExch(f.ticket, 0u);
@@ -253,6 +289,85 @@ __device__ __forceinline__ void dxsum_tail(double* rep, int nrep, int C, float* 
   if (threadIdx.x == 0) atomicExch(ticket, 0u);
 }
 
+// backward sums [NREP][C][3] (NS = 2: the row walk has no token column; the third column is written only when `fill`), then the
+// fused tail
+template <int NS, int EPC>
+__device__ __forceinline__ void flush_bwd_sums(float* red, int cpv, int nlane, int C, const float (&s)[NS][EPC], int fill, double* bsum,
+                                               const BwdFin& fin) {
+  double a[NS][EPC];
+  if (lane_fold(red, cpv, nlane, s, a)) {
+    double* br = bsum + (size_t)(blockIdx.x % NREP) * C * 3;
+#pragma unroll
+    for (int i = 0; i < EPC; ++i) {
+      const int c = threadIdx.x * EPC + i;
+      atomicAdd(&br[c * 3], a[0][i]); atomicAdd(&br[c * 3 + 1], a[1][i]);
+      if constexpr (NS == 3) { if (fill) atomicAdd(&br[c * 3 + 2], a[2][i]); }
+    }
+  }
+  bwd_reduce_tail(bsum, C, fin);
+}
+
+// fixed-point dxsum replicas [dxrep][C]: one integer atomic per channel per workgroup, then the fused tail
+template <int EPC>
+__device__ __forceinline__ void flush_dxsum(float* red, int cpv, int nlane, int C, const float (&sx)[1][EPC], double* dxsum, int dxrep,
+                                            float* dx_accum, unsigned* dx_ticket) {
+  float a[1][EPC];
+  if (lane_fold(red, cpv, nlane, sx, a)) {
+#pragma unroll
+    for (int i = 0; i < EPC; ++i)
+      atomicAdd((unsigned long long*)&dxsum[(size_t)(blockIdx.x % dxrep) * C + threadIdx.x * EPC + i], (unsigned long long)__double2ll_rn((double)a[0][i] * AM_DX_FIX));
+  }
+  dxsum_tail(dxsum, dxrep, C, dx_accum, dx_ticket);
+}
+
+// ---- backward element arithmetic, shared by the linear and the row-walk kernels (each keeps its own loop) ------------------------
+// The per-thread arrays are plain locals of the kernels, passed by reference, and each kernel still loads its own coefficients: a
+// shared loader (function or struct) changes the register allocation and occupancy of the apply kernels (see the commit that
+// introduced these functions).
+
+// d = dout -> dpre = dout * act'(.): from the saved output chunk `ov` (has_out) or from the pre-activation recomputed from f = x
+// (the same expression as norm_apply_kernel's forward).  Compile-time actv / has_out in the specialised kernels: branch-free.
+template <typename T, int EPC>
+__device__ __forceinline__ void bwd_dpre(float (&d)[EPC], const float (&f)[EPC], const u32x4& ov, int actv, bool has_out,
+                                         const float (&qs)[EPC], const float (&qh)[EPC]) {
+  if (actv == AM_ACT_NONE) return;
+  if (has_out) {
+    float o[EPC];
+    chunk_to_f<T>(ov, o);
+#pragma unroll
+    for (int i = 0; i < EPC; ++i) d[i] *= act_grad(o[i], actv);
+  } else {
+#pragma unroll
+    for (int i = 0; i < EPC; ++i) d[i] *= act_grad_pre(f[i] * qs[i] + qh[i], actv);
+  }
+}
+// s1 += dpre, s2 += dpre * xhat
+template <int EPC>
+__device__ __forceinline__ void bwd_sums(const float (&d)[EPC], const float (&f)[EPC], const float (&mu)[EPC], const float (&rs)[EPC],
+                                         float (&s1)[EPC], float (&s2)[EPC]) {
+#pragma unroll
+  for (int i = 0; i < EPC; ++i) { s1[i] += d[i]; s2[i] += d[i] * (f[i] - mu[i]) * rs[i]; }
+}
+// the apply pass's chunk at element offset `off`: dres = dpre (gradient of the residual branch), dx = k0*dpre - k1 - k2*xhat,
+// sx += the STORED dx (want_sum: the bias gradient of the conv that feeds this norm)
+template <typename T, int EPC>
+__device__ __forceinline__ void bwd_dx(const float (&d)[EPC], const float (&f)[EPC], const float (&mu)[EPC], const float (&rs)[EPC],
+                                       const float (&c0)[EPC], const float (&c1)[EPC], const float (&c2)[EPC], size_t off,
+                                       T* __restrict__ dx, T* __restrict__ dres, bool want_sum, float (&sx)[EPC]) {
+  if (dres) *(u32x4*)(dres + off) = f_to_chunk<T>(d);
+  float r[EPC];
+#pragma unroll
+  for (int i = 0; i < EPC; ++i) r[i] = c0[i] * d[i] - c1[i] - c2[i] * (f[i] - mu[i]) * rs[i];
+  const u32x4 pk = f_to_chunk<T>(r);
+  *(u32x4*)(dx + off) = pk;
+  if (want_sum) {
+    float q[EPC];
+    chunk_to_f<T>(pk, q);
+#pragma unroll
+    for (int i = 0; i < EPC; ++i) sx[i] += q[i];
+  }
+}
+
 // ------------------------------------------------------------------ backward: reduce
 // dpre = dout * act'(out);  bsum[c] = {sum dpre, sum dpre*xhat, sum_{inactive} dout (token grad)}
 template <typename T, int NT = 256, int ACT_ = -1, int OUT_ = 0>
@@ -266,9 +381,12 @@ __global__ __launch_bounds__(NT) void norm_bwd_reduce_kernel(const T* __restrict
   const bool has_out = ACT_ >= 0 ? OUT_ != 0 : out != nullptr;  // the per-element code is then branch-free (the generic form compiled to scalar branches per element)
   __shared__ float red[NT * 3 * 8];
   Walk<T> wk(g.C, NT);
-  float s1[EPC], s2[EPC], s3[EPC], mu[EPC], rs[EPC], qs[EPC], qh[EPC];
+  float s[3][EPC];
 #pragma unroll
-  for (int i = 0; i < EPC; ++i) { s1[i] = s2[i] = s3[i] = 0.f; mu[i] = rs[i] = qs[i] = qh[i] = 0.f; }
+  for (int i = 0; i < EPC; ++i) s[0][i] = s[1][i] = s[2][i] = 0.f;
+  float mu[EPC], rs[EPC], qs[EPC], qh[EPC];
+#pragma unroll
+  for (int i = 0; i < EPC; ++i) mu[i] = rs[i] = qs[i] = qh[i] = 0.f;
   if (wk.live) {
 #pragma unroll
     for (int i = 0; i < EPC; ++i) {
@@ -284,52 +402,21 @@ __global__ __launch_bounds__(NT) void norm_bwd_reduce_kernel(const T* __restrict
       chunk_to_f<T>(*(const u32x4*)(dout + off), d);
       if (!a) {
 #pragma unroll
-        for (int i = 0; i < EPC; ++i) s3[i] += d[i];
+        for (int i = 0; i < EPC; ++i) s[2][i] += d[i];
         continue;
       }
       float f[EPC];
       chunk_to_f<T>(*(const u32x4*)(x + off), f);
-      if (actv != AM_ACT_NONE) {
-        if (has_out) {
-          float o[EPC];
-          chunk_to_f<T>(*(const u32x4*)(out + off), o);
-#pragma unroll
-          for (int i = 0; i < EPC; ++i) d[i] *= act_grad(o[i], actv);
-        } else {                                     // same expression as norm_apply_kernel's forward
-#pragma unroll
-          for (int i = 0; i < EPC; ++i) d[i] *= act_grad_pre(f[i] * qs[i] + qh[i], actv);
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < EPC; ++i) { s1[i] += d[i]; s2[i] += d[i] * (f[i] - mu[i]) * rs[i]; }
+      u32x4 ov{};
+      if (has_out && actv != AM_ACT_NONE) ov = *(const u32x4*)(out + off);
+      bwd_dpre<T>(d, f, ov, actv, has_out, qs, qh);
+      bwd_sums(d, f, mu, rs, s[0], s[1]);
     }
   }
-#pragma unroll
-  for (int i = 0; i < EPC; ++i) {
-    red[(threadIdx.x * 3) * 8 + i] = s1[i]; red[(threadIdx.x * 3 + 1) * 8 + i] = s2[i]; red[(threadIdx.x * 3 + 2) * 8 + i] = s3[i];
-  }
-  __syncthreads();
-  if (threadIdx.x < wk.cpv) {
-    double a1[EPC], a2[EPC], a3[EPC];
-#pragma unroll
-    for (int i = 0; i < EPC; ++i) a1[i] = a2[i] = a3[i] = 0.0;
-    for (int vl = 0; vl < wk.vpp; ++vl) {
-      const int t = vl * wk.cpv + threadIdx.x;
-#pragma unroll
-      for (int i = 0; i < EPC; ++i) { a1[i] += red[(t * 3) * 8 + i]; a2[i] += red[(t * 3 + 1) * 8 + i]; a3[i] += red[(t * 3 + 2) * 8 + i]; }
-    }
-#pragma unroll
-    for (int i = 0; i < EPC; ++i) {
-      const int c = threadIdx.x * EPC + i;
-      double* br = bsum + (size_t)(blockIdx.x % NREP) * g.C * 3;
-      atomicAdd(&br[c * 3], a1[i]); atomicAdd(&br[c * 3 + 1], a2[i]);
-      if (fill) atomicAdd(&br[c * 3 + 2], a3[i]);
-    }
-  }
-  bwd_reduce_tail(bsum, g.C, fin);
+  flush_bwd_sums(red, wk.cpv, wk.vpp, g.C, s, fill, bsum, fin);
 }
 
-// per-channel coefficients of the apply pass + parameter gradients (accumulated into fp32 grads)
+// per-channel coefficients of the apply pass + parameter gradients: the three-launch form of bwd_reduce_tail
 __global__ void norm_bwd_finalize_kernel(const double* bsum, const double* count_ptr, double count_host, int C,
                                          const float* gamma, const float* rstd, float* k0, float* k1, float* k2,
                                          float* dgamma, float* dbeta, float* dtoken, float* dbeta2) {
@@ -338,13 +425,7 @@ __global__ void norm_bwd_finalize_kernel(const double* bsum, const double* count
   const double n = count_ptr ? count_ptr[0] : count_host;
   double b1 = 0.0, b2 = 0.0, b3 = 0.0;
   for (int r = 0; r < NREP; ++r) { const double* q = bsum + ((size_t)r * C + c) * 3; b1 += q[0]; b2 += q[1]; b3 += q[2]; }
-  const float gr = gamma[c] * rstd[c];
-  k0[c] = gr;                                  // dx = k0*dpre - k1 - k2*xhat
-  k1[c] = gr * (float)(b1 / n);
-  k2[c] = gr * (float)(b2 / n);
-  if (dgamma) dgamma[c] += (float)b2;
-  if (dbeta) dbeta[c] += (float)b1;
-  if (dbeta2) dbeta2[c] += (float)b1;             // bias of a conv added AFTER the norm (1x1 shortcut): same sum
+  norm_bwd_coeffs(c, b1, b2, n, gamma, rstd, k0, k1, k2, dgamma, dbeta, dbeta2);
   if (dtoken) dtoken[c] += (float)b3;
 }
 
@@ -363,11 +444,14 @@ __global__ __launch_bounds__(NT) void norm_bwd_apply_kernel(const T* __restrict_
   const bool has_out = ACT_ >= 0 ? OUT_ != 0 : out != nullptr;  // the per-element code is then branch-free (the generic form compiled to scalar branches per element)
   __shared__ float red[NT * 8];
   Walk<T> wk(g.C, NT);
-  float mu[EPC], rs[EPC], c0[EPC], c1[EPC], c2[EPC], sx[EPC], qs[EPC], qh[EPC];
+  float sx[1][EPC];
+#pragma unroll
+  for (int i = 0; i < EPC; ++i) sx[0][i] = 0.f;
+  float mu[EPC], rs[EPC], c0[EPC], c1[EPC], c2[EPC], qs[EPC], qh[EPC];
 #pragma unroll
   for (int i = 0; i < EPC; ++i) {
     const int c = wk.cl * EPC + i;
-    sx[i] = 0.f; qs[i] = qh[i] = 0.f;
+    qs[i] = qh[i] = 0.f;
     if (wk.live) {
       mu[i] = mean[c]; rs[i] = rstd[c]; c0[i] = k0[c]; c1[i] = k1[c]; c2[i] = k2[c];
       if (!has_out && actv != AM_ACT_NONE) { qs[i] = psc[c]; qh[i] = psh[c]; }
@@ -381,47 +465,12 @@ __global__ __launch_bounds__(NT) void norm_bwd_apply_kernel(const T* __restrict_
       float d[EPC], f[EPC];
       chunk_to_f<T>(*(const u32x4*)(dout + off), d);
       chunk_to_f<T>(*(const u32x4*)(x + off), f);
-      if (actv != AM_ACT_NONE) {
-        if (has_out) {
-          float o[EPC];
-          chunk_to_f<T>(*(const u32x4*)(out + off), o);
-#pragma unroll
-          for (int i = 0; i < EPC; ++i) d[i] *= act_grad(o[i], actv);
-        } else {
-#pragma unroll
-          for (int i = 0; i < EPC; ++i) d[i] *= act_grad_pre(f[i] * qs[i] + qh[i], actv);
-        }
-      }
-      if (dres) *(u32x4*)(dres + off) = f_to_chunk<T>(d);
-      float r[EPC];
-#pragma unroll
-      for (int i = 0; i < EPC; ++i) r[i] = c0[i] * d[i] - c1[i] - c2[i] * (f[i] - mu[i]) * rs[i];
-      const u32x4 pk = f_to_chunk<T>(r);
-      *(u32x4*)(dx + off) = pk;
-      if (dxsum) {                                 // bias gradient of the conv that feeds this norm = sum of the STORED dx
-        float q[EPC];
-        chunk_to_f<T>(pk, q);
-#pragma unroll
-        for (int i = 0; i < EPC; ++i) sx[i] += q[i];
-      }
+      u32x4 ov{};
+      if (has_out && actv != AM_ACT_NONE) ov = *(const u32x4*)(out + off);
+      bwd_dpre<T>(d, f, ov, actv, has_out, qs, qh);
+      bwd_dx<T>(d, f, mu, rs, c0, c1, c2, off, dx, dres, dxsum != nullptr, sx[0]);
     }
-  if (dxsum) {                                     // (uniform) fold voxel lanes, one float atomic per channel per workgroup
-#pragma unroll
-    for (int i = 0; i < EPC; ++i) red[threadIdx.x * 8 + i] = sx[i];
-    __syncthreads();
-    if (threadIdx.x < wk.cpv) {
-      float a1[EPC];
-#pragma unroll
-      for (int i = 0; i < EPC; ++i) a1[i] = 0.f;
-      for (int vl = 0; vl < wk.vpp; ++vl)
-#pragma unroll
-        for (int i = 0; i < EPC; ++i) a1[i] += red[(vl * wk.cpv + threadIdx.x) * 8 + i];
-#pragma unroll
-      for (int i = 0; i < EPC; ++i)
-        atomicAdd((unsigned long long*)&dxsum[(size_t)(blockIdx.x % dxrep) * g.C + threadIdx.x * EPC + i], (unsigned long long)__double2ll_rn((double)a1[i] * AM_DX_FIX));
-    }
-    dxsum_tail(dxsum, dxrep, g.C, dx_accum, dx_ticket);
-  }
+  if (dxsum) flush_dxsum(red, wk.cpv, wk.vpp, g.C, sx, dxsum, dxrep, dx_accum, dx_ticket);      // (uniform)
 }
 
 
@@ -432,7 +481,8 @@ __global__ __launch_bounds__(NT) void norm_bwd_apply_kernel(const T* __restrict_
 // patch, b << 24 | pd << 16 | ph << 8 | pw): no per-voxel mask lookup, no integer divisions, no loop iterations spent on the
 // 60 % of the volume that is masked, and every thread keeps UNR independent 16-byte loads in flight.
 // Thread t of a workgroup owns chunk (t % rowchunks) of row lane (t / rowchunks); its channel chunk is t % cpv (rowchunks is a
-// multiple of cpv), the same thread -> channel map as the linear kernels, so the reduction epilogues are shared.
+// multiple of cpv), the same thread -> channel map as the linear kernels: both run the same reduction epilogues (lane_fold and
+// the flush_* functions on top of it) and the same backward element arithmetic (bwd_dpre / bwd_sums / bwd_dx); only the loops differ.
 struct RowGeo {
   int B, D, H, W, C, bs;
   int rowchunks;             // 16-byte chunks per patch row = P * C / EPC  (<= 256)
@@ -534,9 +584,9 @@ __global__ __launch_bounds__(256) void chan_stats_rows_kernel(const T* __restric
   constexpr int EPC = TT<T>::EPC;
   __shared__ float red[256 * 2 * 8];
   RowWalk<T> wk(g);
-  float s1[EPC], s2[EPC];
+  float s[2][EPC];
 #pragma unroll
-  for (int i = 0; i < EPC; ++i) s1[i] = s2[i] = 0.f;
+  for (int i = 0; i < EPC; ++i) s[0][i] = s[1][i] = 0.f;
   if (wk.live)
     for (long rw = wk.row; rw < wk.row_end; rw += (long)UNR * wk.rpp) {
       long v[UNR]; u32x4 xv[UNR];
@@ -550,29 +600,10 @@ __global__ __launch_bounds__(256) void chan_stats_rows_kernel(const T* __restric
         float f[EPC];
         chunk_to_f<T>(xv[u], f);
 #pragma unroll
-        for (int i = 0; i < EPC; ++i) { s1[i] += f[i]; s2[i] += f[i] * f[i]; }
+        for (int i = 0; i < EPC; ++i) { s[0][i] += f[i]; s[1][i] += f[i] * f[i]; }
       }
     }
-#pragma unroll
-  for (int i = 0; i < EPC; ++i) { red[(threadIdx.x * 2) * 8 + i] = s1[i]; red[(threadIdx.x * 2 + 1) * 8 + i] = s2[i]; }
-  __syncthreads();
-  const int nlane = blockDim.x / wk.cpv;
-  if (threadIdx.x < wk.cpv) {
-    double a1[EPC], a2[EPC];
-#pragma unroll
-    for (int i = 0; i < EPC; ++i) a1[i] = a2[i] = 0.0;
-    for (int vl = 0; vl < nlane; ++vl) {
-      const int t = vl * wk.cpv + threadIdx.x;
-#pragma unroll
-      for (int i = 0; i < EPC; ++i) { a1[i] += red[(t * 2) * 8 + i]; a2[i] += red[(t * 2 + 1) * 8 + i]; }
-    }
-#pragma unroll
-    for (int i = 0; i < EPC; ++i) {
-      const int c = threadIdx.x * EPC + i;
-      double* sr = sums + (size_t)(blockIdx.x % NREP) * g.C * 2;
-      atomicAdd(&sr[c * 2], a1[i]); atomicAdd(&sr[c * 2 + 1], a2[i]);
-    }
-  }
+  flush_stats(red, wk.cpv, blockDim.x / wk.cpv, g.C, s, sums);
 }
 
 // backward reduce over the active rows (no fill: the densify norms, whose inactive voxels carry the token gradient, keep the
@@ -587,9 +618,12 @@ __global__ __launch_bounds__(256) void norm_bwd_reduce_rows_kernel(const T* __re
   const bool has_out = ACT_ >= 0 ? OUT_ != 0 : out != nullptr;  // the per-element code is then branch-free (the generic form compiled to scalar branches per element)
   __shared__ float red[256 * 2 * 8];
   RowWalk<T> wk(g);
-  float s1[EPC], s2[EPC], mu[EPC], rs[EPC], qs[EPC], qh[EPC];
+  float s[2][EPC];
 #pragma unroll
-  for (int i = 0; i < EPC; ++i) { s1[i] = s2[i] = 0.f; mu[i] = rs[i] = qs[i] = qh[i] = 0.f; }
+  for (int i = 0; i < EPC; ++i) s[0][i] = s[1][i] = 0.f;
+  float mu[EPC], rs[EPC], qs[EPC], qh[EPC];
+#pragma unroll
+  for (int i = 0; i < EPC; ++i) mu[i] = rs[i] = qs[i] = qh[i] = 0.f;
   if (wk.live) {
 #pragma unroll
     for (int i = 0; i < EPC; ++i) {
@@ -612,43 +646,12 @@ __global__ __launch_bounds__(256) void norm_bwd_reduce_rows_kernel(const T* __re
         if (v[u] < 0) continue;
         float d[EPC], f[EPC];
         chunk_to_f<T>(dv[u], d); chunk_to_f<T>(xv[u], f);
-        if (actv != AM_ACT_NONE) {
-          if (has_out) {
-            float o[EPC];
-            chunk_to_f<T>(ov[u], o);
-#pragma unroll
-            for (int i = 0; i < EPC; ++i) d[i] *= act_grad(o[i], actv);
-          } else {
-#pragma unroll
-            for (int i = 0; i < EPC; ++i) d[i] *= act_grad_pre(f[i] * qs[i] + qh[i], actv);
-          }
-        }
-#pragma unroll
-        for (int i = 0; i < EPC; ++i) { s1[i] += d[i]; s2[i] += d[i] * (f[i] - mu[i]) * rs[i]; }
+        bwd_dpre<T>(d, f, ov[u], actv, has_out, qs, qh);
+        bwd_sums(d, f, mu, rs, s[0], s[1]);
       }
     }
   }
-#pragma unroll
-  for (int i = 0; i < EPC; ++i) { red[(threadIdx.x * 2) * 8 + i] = s1[i]; red[(threadIdx.x * 2 + 1) * 8 + i] = s2[i]; }
-  __syncthreads();
-  const int nlane = blockDim.x / wk.cpv;
-  if (threadIdx.x < wk.cpv) {
-    double a1[EPC], a2[EPC];
-#pragma unroll
-    for (int i = 0; i < EPC; ++i) a1[i] = a2[i] = 0.0;
-    for (int vl = 0; vl < nlane; ++vl) {
-      const int t = vl * wk.cpv + threadIdx.x;
-#pragma unroll
-      for (int i = 0; i < EPC; ++i) { a1[i] += red[(t * 2) * 8 + i]; a2[i] += red[(t * 2 + 1) * 8 + i]; }
-    }
-#pragma unroll
-    for (int i = 0; i < EPC; ++i) {
-      const int c = threadIdx.x * EPC + i;
-      double* br = bsum + (size_t)(blockIdx.x % NREP) * g.C * 3;
-      atomicAdd(&br[c * 3], a1[i]); atomicAdd(&br[c * 3 + 1], a2[i]);
-    }
-  }
-  bwd_reduce_tail(bsum, g.C, fin);
+  flush_bwd_sums(red, wk.cpv, blockDim.x / wk.cpv, g.C, s, 0, bsum, fin);
 }
 
 template <typename T, int ACT_ = -1, int OUT_ = 0>
@@ -664,11 +667,14 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_rows_kernel(const T* __res
   const bool has_out = ACT_ >= 0 ? OUT_ != 0 : out != nullptr;  // the per-element code is then branch-free (the generic form compiled to scalar branches per element)
   __shared__ float red[256 * 8];
   RowWalk<T> wk(g);
-  float mu[EPC], rs[EPC], c0[EPC], c1[EPC], c2[EPC], sx[EPC], qs[EPC], qh[EPC];
+  float sx[1][EPC];
+#pragma unroll
+  for (int i = 0; i < EPC; ++i) sx[0][i] = 0.f;
+  float mu[EPC], rs[EPC], c0[EPC], c1[EPC], c2[EPC], qs[EPC], qh[EPC];
 #pragma unroll
   for (int i = 0; i < EPC; ++i) {
     const int c = wk.cl * EPC + i;
-    sx[i] = 0.f; qs[i] = qh[i] = 0.f;
+    qs[i] = qh[i] = 0.f;
     if (wk.live) {
       mu[i] = mean[c]; rs[i] = rstd[c]; c0[i] = k0[c]; c1[i] = k1[c]; c2[i] = k2[c];
       if (!has_out && actv != AM_ACT_NONE) { qs[i] = psc[c]; qh[i] = psh[c]; }
@@ -692,49 +698,11 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_rows_kernel(const T* __res
         const size_t off = (size_t)v[u] * g.C + wk.cl * EPC;
         float d[EPC], f[EPC];
         chunk_to_f<T>(dv[u], d); chunk_to_f<T>(xv[u], f);
-        if (actv != AM_ACT_NONE) {
-          if (has_out) {
-            float o[EPC];
-            chunk_to_f<T>(ov[u], o);
-#pragma unroll
-            for (int i = 0; i < EPC; ++i) d[i] *= act_grad(o[i], actv);
-          } else {
-#pragma unroll
-            for (int i = 0; i < EPC; ++i) d[i] *= act_grad_pre(f[i] * qs[i] + qh[i], actv);
-          }
-        }
-        if (dres) *(u32x4*)(dres + off) = f_to_chunk<T>(d);
-        float r[EPC];
-#pragma unroll
-        for (int i = 0; i < EPC; ++i) r[i] = c0[i] * d[i] - c1[i] - c2[i] * (f[i] - mu[i]) * rs[i];
-        const u32x4 pk = f_to_chunk<T>(r);
-        *(u32x4*)(dx + off) = pk;
-        if (dxsum) {
-          float q[EPC];
-          chunk_to_f<T>(pk, q);
-#pragma unroll
-          for (int i = 0; i < EPC; ++i) sx[i] += q[i];
-        }
+        bwd_dpre<T>(d, f, ov[u], actv, has_out, qs, qh);
+        bwd_dx<T>(d, f, mu, rs, c0, c1, c2, off, dx, dres, dxsum != nullptr, sx[0]);
       }
     }
-  if (dxsum) {
-#pragma unroll
-    for (int i = 0; i < EPC; ++i) red[threadIdx.x * 8 + i] = sx[i];
-    __syncthreads();
-    const int nlane = blockDim.x / wk.cpv;
-    if (threadIdx.x < wk.cpv) {
-      float a1[EPC];
-#pragma unroll
-      for (int i = 0; i < EPC; ++i) a1[i] = 0.f;
-      for (int vl = 0; vl < nlane; ++vl)
-#pragma unroll
-        for (int i = 0; i < EPC; ++i) a1[i] += red[(vl * wk.cpv + threadIdx.x) * 8 + i];
-#pragma unroll
-      for (int i = 0; i < EPC; ++i)
-        atomicAdd((unsigned long long*)&dxsum[(size_t)(blockIdx.x % dxrep) * g.C + threadIdx.x * EPC + i], (unsigned long long)__double2ll_rn((double)a1[i] * AM_DX_FIX));
-    }
-    dxsum_tail(dxsum, dxrep, g.C, dx_accum, dx_ticket);
-  }
+  if (dxsum) flush_dxsum(red, wk.cpv, blockDim.x / wk.cpv, g.C, sx, dxsum, dxrep, dx_accum, dx_ticket);      // (uniform)
 }
 
 // active-patch list of a patch mask: list[i] = b << 24 | pd << 16 | ph << 8 | pw of the i-th active patch in memory order (ONE
@@ -776,9 +744,9 @@ __global__ __launch_bounds__(NT) void chan_sum_kernel(const T* __restrict__ x, G
   constexpr int EPC = TT<T>::EPC;
   __shared__ float red[NT * 8];
   Walk<T> wk(g.C, NT);
-  float s1[EPC];
+  float s[1][EPC], a[1][EPC];
 #pragma unroll
-  for (int i = 0; i < EPC; ++i) s1[i] = 0.f;
+  for (int i = 0; i < EPC; ++i) s[0][i] = 0.f;
   const long v0 = (long)blockIdx.x * g.vpw, v1 = min(v0 + (long)g.vpw, g.nvox());
   if (wk.live)
     for (long v = v0 + wk.vl; v < v1; v += wk.vpp) {
@@ -786,20 +754,11 @@ __global__ __launch_bounds__(NT) void chan_sum_kernel(const T* __restrict__ x, G
       float f[EPC];
       chunk_to_f<T>(*(const u32x4*)(x + v * g.C + wk.cl * EPC), f);
 #pragma unroll
-      for (int i = 0; i < EPC; ++i) s1[i] += f[i];
+      for (int i = 0; i < EPC; ++i) s[0][i] += f[i];
     }
+  if (lane_fold(red, wk.cpv, wk.vpp, s, a)) {
 #pragma unroll
-  for (int i = 0; i < EPC; ++i) red[threadIdx.x * 8 + i] = s1[i];
-  __syncthreads();
-  if (threadIdx.x < wk.cpv) {
-    float a1[EPC];
-#pragma unroll
-    for (int i = 0; i < EPC; ++i) a1[i] = 0.f;
-    for (int vl = 0; vl < wk.vpp; ++vl)
-#pragma unroll
-      for (int i = 0; i < EPC; ++i) a1[i] += red[(vl * wk.cpv + threadIdx.x) * 8 + i];
-#pragma unroll
-    for (int i = 0; i < EPC; ++i) atomicAdd(&out[threadIdx.x * EPC + i], a1[i]);
+    for (int i = 0; i < EPC; ++i) atomicAdd(&out[threadIdx.x * EPC + i], a[0][i]);
   }
 }
 
@@ -1323,9 +1282,9 @@ __global__ __launch_bounds__(256) void proj_norm_bwd_reduce_kernel(const T* __re
   __shared__ float redb[4];
   __shared__ double s0sh;
   Walk<T> wk(C);
-  float s1[EPC], mu[EPC], sb = 0.f;
+  float s1[1][EPC], mu[EPC], sb = 0.f;
 #pragma unroll
-  for (int i = 0; i < EPC; ++i) { s1[i] = 0.f; mu[i] = wk.live ? mean[wk.cl * EPC + i] : 0.f; }
+  for (int i = 0; i < EPC; ++i) { s1[0][i] = 0.f; mu[i] = wk.live ? mean[wk.cl * EPC + i] : 0.f; }
   const long v0 = (long)blockIdx.x * vpw, v1 = min(v0 + (long)vpw, nvox);
   if (wk.live)
     for (long v = v0 + wk.vl; v < v1; v += wk.vpp) {
@@ -1333,24 +1292,16 @@ __global__ __launch_bounds__(256) void proj_norm_bwd_reduce_kernel(const T* __re
       float f[EPC];
       chunk_to_f<T>(*(const u32x4*)(x + (size_t)v * C + wk.cl * EPC), f);
 #pragma unroll
-      for (int i = 0; i < EPC; ++i) s1[i] += d * (f[i] - mu[i]);
+      for (int i = 0; i < EPC; ++i) s1[0][i] += d * (f[i] - mu[i]);
       if (wk.cl == 0) sb += d;
     }
-#pragma unroll
-  for (int i = 0; i < EPC; ++i) red[threadIdx.x * 8 + i] = s1[i];
   sb = warp_sum(sb);
-  if ((threadIdx.x & 63) == 0) redb[threadIdx.x >> 6] = sb;
-  __syncthreads();
+  if ((threadIdx.x & 63) == 0) redb[threadIdx.x >> 6] = sb;      // (before the fold: its barrier covers redb too)
   double* ar = acc + (size_t)(blockIdx.x % NREP) * (C + 1);
-  if (threadIdx.x < wk.cpv) {
-    double a1[EPC];
+  double a1[1][EPC];
+  if (lane_fold(red, wk.cpv, wk.vpp, s1, a1)) {
 #pragma unroll
-    for (int i = 0; i < EPC; ++i) a1[i] = 0.0;
-    for (int vl = 0; vl < wk.vpp; ++vl)
-#pragma unroll
-      for (int i = 0; i < EPC; ++i) a1[i] += red[(vl * wk.cpv + threadIdx.x) * 8 + i];
-#pragma unroll
-    for (int i = 0; i < EPC; ++i) atomicAdd(&ar[threadIdx.x * EPC + i], a1[i]);
+    for (int i = 0; i < EPC; ++i) atomicAdd(&ar[threadIdx.x * EPC + i], a1[0][i]);
   }
   if (threadIdx.x == 0) atomicAdd(&ar[C], (double)redb[0] + (double)redb[1] + (double)redb[2] + (double)redb[3]);
   // ---- last workgroup: coefficients of the apply pass + the four parameter gradients; accumulators re-zeroed
@@ -1412,9 +1363,9 @@ __global__ __launch_bounds__(256) void proj_bwd_kernel(const T* __restrict__ x, 
   __shared__ float red[256 * 8];
   __shared__ float redb[4];
   Walk<T> wk(C);
-  float sw[EPC], wv[EPC], sb = 0.f;
+  float sw[1][EPC], wv[EPC], sb = 0.f;
 #pragma unroll
-  for (int i = 0; i < EPC; ++i) { sw[i] = 0.f; wv[i] = wk.live ? w[wk.cl * EPC + i] : 0.f; }
+  for (int i = 0; i < EPC; ++i) { sw[0][i] = 0.f; wv[i] = wk.live ? w[wk.cl * EPC + i] : 0.f; }
   const long v0 = (long)blockIdx.x * vpw, v1 = min(v0 + (long)vpw, nvox);
   if (wk.live)
     for (long v = v0 + wk.vl; v < v1; v += wk.vpp) {
@@ -1423,26 +1374,18 @@ __global__ __launch_bounds__(256) void proj_bwd_kernel(const T* __restrict__ x, 
       float f[EPC], o[EPC];
       chunk_to_f<T>(*(const u32x4*)(x + off), f);
 #pragma unroll
-      for (int i = 0; i < EPC; ++i) { sw[i] += d * f[i]; o[i] = d * wv[i]; }
+      for (int i = 0; i < EPC; ++i) { sw[0][i] += d * f[i]; o[i] = d * wv[i]; }
       *(u32x4*)(dx + off) = f_to_chunk<T>(o);
       if (wk.cl == 0) sb += d;
     }
-#pragma unroll
-  for (int i = 0; i < EPC; ++i) red[threadIdx.x * 8 + i] = sw[i];
   sb = warp_sum(sb);
-  if ((threadIdx.x & 63) == 0) redb[threadIdx.x >> 6] = sb;
-  __syncthreads();
-  if (threadIdx.x < wk.cpv) {
-    float a1[EPC];
-#pragma unroll
-    for (int i = 0; i < EPC; ++i) a1[i] = 0.f;
-    for (int vl = 0; vl < wk.vpp; ++vl)
-#pragma unroll
-      for (int i = 0; i < EPC; ++i) a1[i] += red[(vl * wk.cpv + threadIdx.x) * 8 + i];
+  if ((threadIdx.x & 63) == 0) redb[threadIdx.x >> 6] = sb;      // (before the fold: its barrier covers redb too)
+  float a1[1][EPC];
+  if (lane_fold(red, wk.cpv, wk.vpp, sw, a1)) {
 #pragma unroll
     for (int i = 0; i < EPC; ++i) {
-      if (det_ws) det_ws[(size_t)blockIdx.x * (C + 1) + threadIdx.x * EPC + i] = a1[i];    // deterministic mode: a row per workgroup, folded in order
-      else atomicAdd(&dw[threadIdx.x * EPC + i], a1[i]);
+      if (det_ws) det_ws[(size_t)blockIdx.x * (C + 1) + threadIdx.x * EPC + i] = a1[0][i];    // deterministic mode: a row per workgroup, folded in order
+      else atomicAdd(&dw[threadIdx.x * EPC + i], a1[0][i]);
     }
   }
   if (threadIdx.x == 0) {
@@ -1689,26 +1632,12 @@ __global__ __launch_bounds__(256) void partials_finalize_kernel(const float* __r
     }
     if (sum_accum) sum_accum[c] += (float)q1;
     if (k0) {                                                  // bsum of norm_bwd_reduce: b1 = sum g, b2 = sum g * xhat = rstd * (sum g*x - mean * sum g)
-      const double b1 = q1, b2 = (double)bw_rstd[c] * (q2 - (double)bw_mean[c] * q1);
-      const float gr = gamma[c] * bw_rstd[c];
-      k0[c] = gr; k1[c] = gr * (float)(b1 / n); k2[c] = gr * (float)(b2 / n);
-      if (dgamma) dgamma[c] += (float)b2;
-      if (dbeta) dbeta[c] += (float)b1;
-      if (dbeta2) dbeta2[c] += (float)b1;
+      const double b2 = (double)bw_rstd[c] * (q2 - (double)bw_mean[c] * q1);
+      norm_bwd_coeffs(c, q1, b2, n, gamma, bw_rstd, k0, k1, k2, dgamma, dbeta, dbeta2);
       continue;
     }
     if (!gamma) continue;
-    const double m = q1 / n;
-    double var = q2 / n - m * m;
-    if (var < 0) var = 0;
-    const float rs = (float)(1.0 / sqrt(var + (double)eps));
-    mean[c] = (float)m; rstd[c] = rs;
-    const float scv = gamma[c] * rs;
-    scale[c] = scv; shift[c] = beta[c] - (float)m * scv;
-    if (run_mean) {
-      run_mean[c] = (1.f - momentum) * run_mean[c] + momentum * (float)m;
-      run_var[c] = (1.f - momentum) * run_var[c] + momentum * (float)(var * (n / (n - 1.0)));
-    }
+    norm_coeffs(c, q1, q2, n, gamma, beta, eps, mean, rstd, scale, shift, run_mean, run_var, momentum);
   }
   if (t == 0) { atomicExch(ticket, 0u); if (nbt) nbt[0] += 1; }
 }
@@ -1716,9 +1645,13 @@ __global__ __launch_bounds__(256) void partials_finalize_kernel(const float* __r
 // voxels per workgroup: whole passes (256/(C/EPC) voxels each), ~2048 workgroups per launch (<= 1024 for reductions)
 // threads per workgroup of the linear (Walk) kernels: a voxel row of more than 256 16-byte chunks (fp32, C > 1024) takes 512
 inline int walk_threads(int C, int dtype) { return C / (dtype == AM_DT_BF16 ? 8 : 4) > 256 ? 512 : 256; }
+// voxels per pass of those kernels
+inline int walk_vpp(int C, int dtype) {
+  const int vpp = walk_threads(C, dtype) / (C / (dtype == AM_DT_BF16 ? 8 : 4));
+  return vpp < 1 ? 1 : vpp;
+}
 inline int pick_vpw(long nvox, int C, int dtype, bool reduction) {
-  const int epc = dtype == AM_DT_BF16 ? 8 : 4;
-  int vpp = walk_threads(C, dtype) / (C / epc); if (vpp < 1) vpp = 1;
+  const int vpp = walk_vpp(C, dtype);
   long target = reduction ? 1024 : 2048;
 #ifdef AM_ABLATE
   if (const char* e = getenv(reduction ? "AM_RED_TARGET" : "AM_MAP_TARGET")) target = atol(e);
@@ -1773,6 +1706,14 @@ inline bool mkrows(RowGeo& r, int dtype, bool reduction, int B, int D, int H, in
 }
 inline int rows_blocks(const RowGeo& r) { return (int)((r.total_rows + r.rpw - 1) / r.rpw); }
 inline int rows_threads(const RowGeo& r) { return r.rpp * r.rowchunks; }
+
+// launch of partials_finalize_kernel: nb workgroups (<= 2048) of rpb rows each, rpb a whole number of the workgroup's row lanes
+inline void partials_grid(int rows, int C, int& nb, int& rpb) {
+  const int cp = C / 2, rstep = cp <= 256 ? 256 / cp : 1;
+  nb = rows / (rstep * 8); nb = nb < 1 ? 1 : (nb > 2048 ? 2048 : nb);
+  rpb = ((rows + nb - 1) / nb + rstep - 1) / rstep * rstep;
+  nb = (rows + rpb - 1) / rpb;
+}
 
 }  // namespace
 
@@ -1977,7 +1918,7 @@ int am_chan_sum(int dtype, const void* x, int B, int D, int H, int W, int C, con
   hipStream_t st = (hipStream_t)stream;
   // small tensors (the densify projection of the coarsest level: its bias gradient): ONE workgroup, so the fp32 sum has a fixed order
   // (with several workgroups the per-workgroup sums arrive as fp32 atomics in any order)
-  if ((long)B * D * H * W * C <= (4L << 20)) { g.vpw = (int)((long)B * D * H * W); const int vpp = walk_threads(C, dtype) / (C / (dtype == AM_DT_BF16 ? 8 : 4)) > 0 ? walk_threads(C, dtype) / (C / (dtype == AM_DT_BF16 ? 8 : 4)) : 1; g.vpw = (g.vpw + vpp - 1) / vpp * vpp; }
+  if ((long)B * D * H * W * C <= (4L << 20)) { const int vpp = walk_vpp(C, dtype); g.vpw = ((int)((long)B * D * H * W) + vpp - 1) / vpp * vpp; }
   const int nb = nblk((long)B * D * H * W, g.vpw);
   am_by_walk(dtype, C, [&](auto t, auto nt) {
     using T = typename decltype(t)::type;
@@ -2160,10 +2101,8 @@ int am_partials_finalize(const float* partials, int rows, int C, double* workspa
   if (C <= 0 || C > 4096 || rows <= 0 || !workspace) return -1;
   if (gamma && (!beta || !mean || !rstd || !scale || !shift)) return -1;
   if (C % 2) return -1;
-  const int cp = C / 2, rstep = cp <= 256 ? 256 / cp : 1;
-  int nb = rows / (rstep * 8); nb = nb < 1 ? 1 : (nb > 2048 ? 2048 : nb);
-  const int rpb = ((rows + nb - 1) / nb + rstep - 1) / rstep * rstep;
-  nb = (rows + rpb - 1) / rpb;
+  int nb, rpb;
+  partials_grid(rows, C, nb, rpb);
   AM_LAUNCH(partials_finalize_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, partials, rows, C, rpb, workspace, count_ptr, count_host,
             gamma, beta, eps, mean, rstd, scale, shift, run_mean, run_var, momentum, num_batches_tracked, sum_accum,
             (const float*)nullptr, (const float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr);
@@ -2178,10 +2117,8 @@ int am_norm_bwd_from_partials(const float* partials, int rows, int C, double* wo
                               const float* gamma, const float* mean, const float* rstd, float* k0, float* k1, float* k2,
                               float* dgamma, float* dbeta, float* dbeta2, void* stream) {
   if (C <= 0 || C > 4096 || C % 2 || rows <= 0 || !workspace || !gamma || !mean || !rstd || !k0 || !k1 || !k2) return -1;
-  const int cp = C / 2, rstep = cp <= 256 ? 256 / cp : 1;
-  int nb = rows / (rstep * 8); nb = nb < 1 ? 1 : (nb > 2048 ? 2048 : nb);
-  const int rpb = ((rows + nb - 1) / nb + rstep - 1) / rstep * rstep;
-  nb = (rows + rpb - 1) / rpb;
+  int nb, rpb;
+  partials_grid(rows, C, nb, rpb);
   AM_LAUNCH(partials_finalize_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, partials, rows, C, rpb, workspace, count_ptr, count_host,
             gamma, (const float*)nullptr, 0.f, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr,
             0.f, (long*)nullptr, (float*)nullptr, mean, rstd, k0, k1, k2, dgamma, dbeta, dbeta2);

@@ -121,14 +121,12 @@ class ConvPartials:
         launch (am_partials_finalize); st None: only `sum_accum[c] += sum` (bias gradients)."""
         assert st is None or not self.sum_only, "sum-only rows carry no sum of squares"
         ws = _stats_workspace(self.t.device, self.C)
-        if st is None:
-            hip.lib().partials_finalize(self.t.data_ptr(), self.rows, self.C, ws.data_ptr(), None, 1.0, None, None, 0.0, None, None, None,
-                                        None, None, None, 0.0, None, _p(sum_accum), _stream())
-            return
-        hip.lib().partials_finalize(self.t.data_ptr(), self.rows, self.C, ws.data_ptr(), _p(st.count_ptr), float(st.count_host),
-                                    gamma.data_ptr(), beta.data_ptr(), eps, st.mean.data_ptr(), st.rstd.data_ptr(), st.scale.data_ptr(),
-                                    st.shift.data_ptr(), _p(run_mean), _p(run_var), momentum, _p(num_batches_tracked), _p(sum_accum), _stream())
-        st.nrep = 1
+        norm = (None, 1.0, None, None, 0.0, None, None, None, None, None, None, 0.0, None) if st is None else (
+            _p(st.count_ptr), float(st.count_host), gamma.data_ptr(), beta.data_ptr(), eps, st.mean.data_ptr(), st.rstd.data_ptr(),
+            st.scale.data_ptr(), st.shift.data_ptr(), _p(run_mean), _p(run_var), momentum, _p(num_batches_tracked))
+        hip.lib().partials_finalize(self.t.data_ptr(), self.rows, self.C, ws.data_ptr(), *norm, _p(sum_accum), _stream())
+        if st is not None:
+            st.nrep = 1
 
 
     def finalize_bwd(self, st: "NormStats", gamma: torch.Tensor, sc: "NormBwdScratch", dgamma=None, dbeta=None, dbeta2=None):
@@ -473,63 +471,44 @@ def norm_backward(dout: torch.Tensor, out: Optional[torch.Tensor], x: torch.Tens
     reduced: the partial rows of the conv3d(norm_bwd=(x, st, act)) launch that produced dout -- the reduce pass is skipped."""
     B, D, H, W, Cc = x.shape
     sc = scratch or NormBwdScratch(Cc, x.device)
-    mp, fd, fh, fw = _mk(mask)
     L = hip.lib()
     s = _stream()
     ws_b, ws_x = _bwd_workspaces(x.device, Cc)
+    mp, fd, fh, fw = _mk(mask)
+    geo = (B, D, H, W, Cc, mp, bshift, fd, fh, fw)
+    k = [sc.k[i].data_ptr() for i in range(3)]
+    grads = (_p(dgamma), _p(dbeta), _p(dtoken), _p(dbeta2))
+    sync = st.sync_world > 1
+    # the reduce's last workgroup folds the sums into k0/k1/k2 and the parameter gradients, unless the sums have to be all-reduced
+    # first (SyncBatchNorm) or the three-launch form is asked for (tools/step_ab.py: same-process A/B timing)
+    fused_tail = FUSED_BWD_TAILS and not sync
+    need_finalize = reduced is None and not fused_tail       # a separate norm_bwd_finalize launch
     if reduced is not None:
-        assert st.sync_world <= 1 and out is None and dtoken is None and not fill
+        assert not sync and out is None and dtoken is None and not fill
         reduced.finalize_bwd(st, gamma, sc, dgamma, dbeta, dbeta2)
-        if dx is None:
-            dx = torch.empty_like(x)
-        L.norm_bwd_apply(_dt(x), dout.data_ptr(), None, x.data_ptr(), B, D, H, W, Cc, mp, bshift, fd, fh, fw,
-                         st.mean.data_ptr(), st.rstd.data_ptr(), sc.k[0].data_ptr(), sc.k[1].data_ptr(), sc.k[2].data_ptr(), act,
-                         dx.data_ptr(), _p(dres), _p(dxsum), ws_x.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr(), *_al(mask), 1, s)
-        return dx
-    if st.sync_world > 1:
-        # SyncBatchNorm backward (torch.nn.SyncBatchNorm): dx needs the sums over the GLOBAL batch, the affine gradients stay LOCAL
-        # sums (DDP then averages them like every other gradient): reduce -> finalize (param grads) -> all-reduce -> finalize (k's)
-        import torch.distributed as dist
-        L.norm_bwd_reduce(_dt(x), dout.data_ptr(), _p(out), x.data_ptr(), B, D, H, W, Cc, mp, bshift, fd, fh, fw,
-                          st.mean.data_ptr(), st.rstd.data_ptr(), act, int(fill), ws_b.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr(),
-                          *_al(mask), None, 0.0, None, None, None, None, None, None, None, None, s)
-        L.norm_bwd_finalize(ws_b.data_ptr(), None, float(st.count_host), Cc, gamma.data_ptr(), st.rstd.data_ptr(),
-                            sc.k[0].data_ptr(), sc.k[1].data_ptr(), sc.k[2].data_ptr(), _p(dgamma), _p(dbeta), _p(dtoken), _p(dbeta2), s)
-        dist.all_reduce(ws_b[:NREP * Cc * 3])
-        L.norm_bwd_finalize(ws_b.data_ptr(), None, float(st.count_host), Cc, gamma.data_ptr(), st.rstd.data_ptr(),
-                            sc.k[0].data_ptr(), sc.k[1].data_ptr(), sc.k[2].data_ptr(), None, None, None, None, s)
-        ws_b[:NREP * Cc * 3].zero_()                                   # the workspace contract: left zero
-        if dx is None:
-            dx = torch.empty_like(x)
-        L.norm_bwd_apply(_dt(x), dout.data_ptr(), _p(out), x.data_ptr(), B, D, H, W, Cc, mp, bshift, fd, fh, fw,
-                         st.mean.data_ptr(), st.rstd.data_ptr(), sc.k[0].data_ptr(), sc.k[1].data_ptr(), sc.k[2].data_ptr(), act,
-                         dx.data_ptr(), _p(dres), _p(dxsum), ws_x.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr(), *_al(mask), 1, s)
-        return dx
-    if not FUSED_BWD_TAILS:                      # (tools/step_ab.py: the three-launch form, for same-process A/B timing)
-        L.norm_bwd_reduce(_dt(x), dout.data_ptr(), _p(out), x.data_ptr(), B, D, H, W, Cc, mp, bshift, fd, fh, fw,
-                          st.mean.data_ptr(), st.rstd.data_ptr(), act, int(fill), ws_b.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr(),
-                          *_al(mask), None, 0.0, None, None, None, None, None, None, None, None, s)
-        L.norm_bwd_finalize(ws_b.data_ptr(), _p(st.count_ptr), float(st.count_host), Cc, gamma.data_ptr(), st.rstd.data_ptr(),
-                            sc.k[0].data_ptr(), sc.k[1].data_ptr(), sc.k[2].data_ptr(), _p(dgamma), _p(dbeta), _p(dtoken), _p(dbeta2), s)
-        ws_b[:NREP * Cc * 3].zero_()                                   # the shared workspaces' contract: zero on entry, LEFT zero
-        if dx is None:
-            dx = torch.empty_like(x)
-        L.norm_bwd_apply(_dt(x), dout.data_ptr(), _p(out), x.data_ptr(), B, D, H, W, Cc, mp, bshift, fd, fh, fw,
-                         st.mean.data_ptr(), st.rstd.data_ptr(), sc.k[0].data_ptr(), sc.k[1].data_ptr(), sc.k[2].data_ptr(), act,
-                         dx.data_ptr(), _p(dres), _p(dxsum), ws_x.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr(), *_al(mask), 0, s)
-        if dxsum is not None:
-            ws_x[:DXREP * Cc].zero_()
-        return dx
-    # reduce + finalize in ONE launch (the last workgroup folds the sums into k0/k1/k2 and the parameter gradients)
-    L.norm_bwd_reduce(_dt(x), dout.data_ptr(), _p(out), x.data_ptr(), B, D, H, W, Cc, mp, bshift, fd, fh, fw,
-                      st.mean.data_ptr(), st.rstd.data_ptr(), act, int(fill), ws_b.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr(),
-                      *_al(mask), _p(st.count_ptr), float(st.count_host), gamma.data_ptr(), sc.k[0].data_ptr(), sc.k[1].data_ptr(),
-                      sc.k[2].data_ptr(), _p(dgamma), _p(dbeta), _p(dtoken), _p(dbeta2), s)
+    else:
+        fin = (_p(st.count_ptr), float(st.count_host), gamma.data_ptr(), *k, *grads) if fused_tail else (None, 0.0) + (None,) * 8
+        L.norm_bwd_reduce(_dt(x), dout.data_ptr(), _p(out), x.data_ptr(), *geo, st.mean.data_ptr(), st.rstd.data_ptr(), act, int(fill),
+                          ws_b.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr(), *_al(mask), *fin, s)
+    if need_finalize:
+        bsum = ws_b[:NREP * Cc * 3]
+        # SyncBatchNorm backward (torch.nn.SyncBatchNorm): dx needs the sums over the GLOBAL batch (count_host), the affine gradients stay
+        # LOCAL sums (DDP then averages them like every other gradient): reduce -> finalize (param grads) -> all-reduce -> finalize (k's)
+        L.norm_bwd_finalize(ws_b.data_ptr(), None if sync else _p(st.count_ptr), float(st.count_host), Cc, gamma.data_ptr(),
+                            st.rstd.data_ptr(), *k, *grads, s)
+        if sync:
+            import torch.distributed as dist
+            dist.all_reduce(bsum)
+            L.norm_bwd_finalize(ws_b.data_ptr(), None, float(st.count_host), Cc, gamma.data_ptr(), st.rstd.data_ptr(), *k,
+                                None, None, None, None, s)
+        bsum.zero_()                                                   # the shared workspaces' contract: zero on entry, LEFT zero
     if dx is None:
         dx = torch.empty_like(x)
-    L.norm_bwd_apply(_dt(x), dout.data_ptr(), _p(out), x.data_ptr(), B, D, H, W, Cc, mp, bshift, fd, fh, fw,
-                     st.mean.data_ptr(), st.rstd.data_ptr(), sc.k[0].data_ptr(), sc.k[1].data_ptr(), sc.k[2].data_ptr(), act,
-                     dx.data_ptr(), _p(dres), _p(dxsum), ws_x.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr(), *_al(mask), 1, s)
+    zero_ws = sync or not need_finalize                      # ws_x is the zero workspace: the apply's last workgroup folds the dxsum replicas itself
+    L.norm_bwd_apply(_dt(x), dout.data_ptr(), _p(out), x.data_ptr(), *geo, st.mean.data_ptr(), st.rstd.data_ptr(), *k, act,
+                     dx.data_ptr(), _p(dres), _p(dxsum), ws_x.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr(), *_al(mask), int(zero_ws), s)
+    if dxsum is not None and not zero_ws:
+        ws_x[:DXREP * Cc].zero_()
     return dx
 
 

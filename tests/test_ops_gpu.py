@@ -3,6 +3,8 @@ Tolerances (stated per dtype):
   fp32 path (exact-f32 MFMA, fp32 storage):   <= 2e-4 of the tensor's max |value|  (reduction order only)
   bf16 path (bf16 storage, fp32 accumulate):  <= 2e-2 of max |value|, inputs pre-rounded to bf16 on both sides
 Integer/bool outputs (sampler masks) are bit-exact."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -1069,6 +1071,95 @@ def test_batchnorm_train_eval_relu6(ops, dtype, C):
     ops.norm_fold_running(st, p["bn.weight"].detach().to(DEV), p["bn.bias"].detach().to(DEV), p["bn.running_mean"].to(DEV),
                           p["bn.running_var"].to(DEV), 1e-5)
     close(from_cl(ops.norm_apply(xd, st, ops.ACT_NONE)), ye, TOL[dtype], "BN eval")
+
+
+NB_PATHS = {"dense": (40, False),            # no mask: linear kernels; 5 / 10 chunks per voxel leave 1 / 6 idle threads
+            "rows": (16, True),              # active-patch row walk: 160 patch rows in 2 (bf16) / 3 (fp32) workgroups, the last one ragged
+            "masked_linear": (520, True)}    # rows of 260 / 520 chunks: too wide for the row walk, masked linear kernels, 61 / 126 idle threads
+NB_GATES = ["none", "lrelu_saved", "lrelu_recomputed", "relu6_recomputed"]
+
+
+@functools.lru_cache(maxsize=None)
+def _norm_bwd_reference(dtype, path, gate):
+    """fp64 autograd of y = act(IN(x) + res) on the geometry of test_sparse_instance_norm_fwd_bwd (dense: every patch active).
+    Returns the inputs, the gradients, `keep` (active voxels off the gate's knife edges) and the share of active elements left out."""
+    C, sparse = NB_PATHS[path]
+    B, f = 2, (2, 2, 3)
+    sp = tuple(v * 4 for v in f)
+    mask = torch.ones(B, 1, *f, dtype=torch.bool)
+    if sparse:
+        mask[:] = False
+        mask.view(B, -1)[0, :3] = True; mask.view(B, -1)[1, 2:9] = True
+    mf = O.upsample_mask(mask, sp).double()
+    relu6, saved = gate == "relu6_recomputed", gate == "lrelu_saved"
+    x = (q(rnd(B, C, *sp, seed=1), dtype).double() * mf).requires_grad_(True)
+    # a recomputed gate belongs to a norm without a residual: res = 0 there, its gradient is still the pre-activation gradient
+    res = ((q(rnd(B, C, *sp, seed=5), dtype).double() if saved else torch.zeros(B, C, *sp, dtype=torch.float64)) * mf).requires_grad_(True)
+    # ReLU6: z ~ N(3, 3^2), so a sixth of the elements sits on either closed side of the gate and few of them near 6
+    gam = ((3.0 if relu6 else 1.0) * (1 + 0.2 * rnd(C, seed=2))).double().requires_grad_(True)
+    bet = ((3.0 if relu6 else 0.0) + 0.1 * rnd(C, seed=3)).double().requires_grad_(True)
+    dout = q(rnd(B, C, *sp, seed=4), dtype).double() * mf
+    z = O.sparse_instance_norm(x, gam, bet, 1e-5, mask) + res
+    y = z if gate == "none" else (F.relu6(z) if relu6 else F.leaky_relu(z, 0.01))
+    y.backward(dout)
+    keep = mf.expand_as(z).clone()
+    zd = z.detach()
+    if gate != "none":
+        keep = keep * (zd.abs() > 1e-3)
+    if relu6:
+        keep = keep * ((zd - 6.0).abs() > 0.03)
+    excluded = 1.0 - keep.sum().item() / mf.expand_as(z).sum().item()
+    return dict(C=C, B=B, sp=sp, mask=mask if sparse else None, mf=mf, x=x.detach(), res=res.detach(), gam=gam.detach(), bet=bet.detach(),
+                dout=dout, y=y.detach(), dx=x.grad, dres=res.grad, dgamma=gam.grad, dbeta=bet.grad, keep=keep, excluded=excluded)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("path", list(NB_PATHS))
+@pytest.mark.parametrize("gate", NB_GATES)
+@pytest.mark.parametrize("fused", [True, False])
+def test_norm_backward_paths(ops, monkeypatch, dtype, path, gate, fused):
+    """norm_backward on the linear, row-walk and masked-linear kernels, each gate source, fused and three-launch tails: dx, dres, the
+    affine gradients and dbeta2 against fp64 autograd; dxsum against the fp64 channel sum of the stored dx."""
+    r = _norm_bwd_reference(dtype, path, gate)
+    assert r["excluded"] < 0.01, f"knife-edge band holds {r['excluded']:.3%} of the active elements"      # (CPU reference alone)
+    monkeypatch.setattr(ops, "FUSED_BWD_TAILS", fused)
+    C, mf = r["C"], r["mf"]
+    mi = ops.MaskInfo.from_bool(r["mask"], DEV) if r["mask"] is not None else None
+    bshift = 2 if mi is not None else 0
+    st = ops.NormStats(C, DEV)
+    if mi is not None:
+        cnt = torch.zeros(1, device=DEV, dtype=torch.float64)
+        ops.mask_count(mi, 64, cnt); st.count_ptr = cnt
+    else:
+        st.count_host = float(mf.sum().item())
+    gam, bet = r["gam"].float().to(DEV), r["bet"].float().to(DEV)
+    xd = to_cl(r["x"].float(), dtype)
+    ops.chan_stats(xd, mi, bshift, st)
+    ops.norm_finalize(st, gam, bet, 1e-5)
+    act = {"none": ops.ACT_NONE, "relu6_recomputed": ops.ACT_RELU6}.get(gate, ops.ACT_LRELU)
+    # saved output: the oracle's own, so both sides take identical gates
+    out = to_cl(r["y"].float(), dtype) if gate == "lrelu_saved" else None
+    dg, db, db2, dxs = (torch.zeros(C, device=DEV) for _ in range(4))
+    dx, dres = torch.zeros_like(xd), torch.zeros_like(xd)
+    ops.norm_backward(to_cl(r["dout"].float(), dtype), out, xd, st, gam, act, mi, bshift, dg, db, dx=dx, dres=dres, dbeta2=db2, dxsum=dxs)
+    tag = f"{path}/{gate}/{'fused' if fused else 'unfused'}"
+    close(from_cl(dx), r["dx"], 2 * TOL[dtype], f"{tag} dx", r["keep"])
+    close(from_cl(dres), r["dres"], TOL[dtype], f"{tag} dres", r["keep"])
+    close(dg.cpu(), r["dgamma"], 2 * TOL[dtype], f"{tag} dgamma")
+    close(db.cpu(), r["dbeta"], 2 * TOL[dtype], f"{tag} dbeta")
+    close(db2.cpu(), r["dbeta"], 2 * TOL[dtype], f"{tag} dbeta2")
+    # dxsum: the channel sum of the STORED dx, added to what the accumulator holds.  With the true count it cancels analytically (only
+    # rounding is left, nothing to compare with), so a second call runs with TWICE the count: k1 and k2 halve and sum dx = k0 * b1 / 2.
+    # It follows the first call on the same workspaces, so a replica that the first call's tail (fused) or the host (unfused) did not
+    # re-zero would show up here as well.
+    if st.count_ptr is not None:
+        st.count_ptr.mul_(2.0)
+    else:
+        st.count_host *= 2.0
+    pre = rnd(C, seed=9)
+    dxs2, dx2 = pre.to(DEV), torch.zeros_like(xd)
+    ops.norm_backward(to_cl(r["dout"].float(), dtype), out, xd, st, gam, act, mi, bshift, None, None, dx=dx2, dxsum=dxs2)
+    close(dxs2.cpu(), pre.double() + (from_cl(dx2).double() * mf).sum(dim=(0, 2, 3, 4)), 2 * TOL[dtype], f"{tag} dxsum")
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
