@@ -6,8 +6,10 @@
 //                         scipy.ndimage.spline_filter(order=3, mode='mirror'), which is what map_coordinates(order=3, mode='constant')
 //                         applies before interpolating (batchgenerators.augmentations.utils.interpolate_img calls map_coordinates)
 //   am_resample_affine    out[o] = interp(src, A * (o, 1)): per-sample 3x4 affine (rotation, scale, centring, mirror flips folded
-//                         in); order 0 = integer crop / flip, 1 = trilinear, 3 = cubic B-spline over prefiltered coefficients with
-//                         scipy's rules (outside [0, n-1] -> cval, mirrored coefficient access at the edges)
+//                         in); order 0 = nearest voxel, floor(x + 0.5) (integer crop / flip when A is one), 1 = trilinear, 3 = cubic
+//                         B-spline over prefiltered coefficients; every order with scipy's map_coordinates(mode='constant') rules:
+//                         a coordinate outside [0, n-1] on any axis -> cval (order 0 too: -0.3 is outside although it rounds to 0),
+//                         mirrored coefficient access at the edges.  Null pointers / non-positive extents / other orders: -2, no launch
 #include "common.h"
 #include "../../include/anatomask_hip.h"
 
@@ -68,12 +70,12 @@ __global__ __launch_bounds__(256) void resample_affine_kernel(const float* __res
   const float py = A.a[4] * d + A.a[5] * h + A.a[6] * w + A.a[7];
   const float px = A.a[8] * d + A.a[9] * h + A.a[10] * w + A.a[11];
   float out = cval;
-  if (order == 0) {
-    const int iz = (int)floorf(pz + 0.5f), iy = (int)floorf(py + 0.5f), ix = (int)floorf(px + 0.5f);
-    if ((unsigned)iz < (unsigned)Ds && (unsigned)iy < (unsigned)Hs && (unsigned)ix < (unsigned)Ws) out = src[((long)iz * Hs + iy) * Ws + ix];
-  } else if (pz >= 0.f && pz <= Ds - 1.f && py >= 0.f && py <= Hs - 1.f && px >= 0.f && px <= Ws - 1.f) {   // scipy: outside [0, n-1] -> cval
+  if (pz >= 0.f && pz <= Ds - 1.f && py >= 0.f && py <= Hs - 1.f && px >= 0.f && px <= Ws - 1.f) {   // scipy: outside [0, n-1] -> cval, every order
     const int bz = (int)floorf(pz), by = (int)floorf(py), bx = (int)floorf(px);
-    if (order == 1) {
+    if (order == 0) {                                              // nearest: floor(p + 0.5), ties upwards
+      const int iz = min((int)floorf(pz + 0.5f), Ds - 1), iy = min((int)floorf(py + 0.5f), Hs - 1), ix = min((int)floorf(px + 0.5f), Ws - 1);
+      out = src[((long)iz * Hs + iy) * Ws + ix];
+    } else if (order == 1) {
       const float fz = pz - bz, fy = py - by, fx = px - bx;
       float s = 0.f;
 #pragma unroll
@@ -111,7 +113,7 @@ __global__ __launch_bounds__(256) void resample_affine_kernel(const float* __res
 extern "C" {
 
 int am_spline_prefilter(float* vol, int D, int H, int W, void* stream) {
-  if (D < 1 || H < 1 || W < 1) return -1;
+  if (!vol || D < 1 || H < 1 || W < 1) return -1;
   hipStream_t st = (hipStream_t)stream;
   for (int axis = 0; axis < 3; ++axis) {
     const long nline = axis == 0 ? (long)H * W : axis == 1 ? (long)D * W : (long)D * H;
@@ -124,6 +126,7 @@ int am_spline_prefilter(float* vol, int D, int H, int W, void* stream) {
 int am_resample_affine(const float* src, int Ds, int Hs, int Ws, float* dst, int D, int H, int W, const float* affine_host12, int order,
                        float cval, void* stream) {
   if (order != 0 && order != 1 && order != 3) return -2;
+  if (!src || !dst || !affine_host12 || Ds <= 0 || Hs <= 0 || Ws <= 0 || D <= 0 || H <= 0 || W <= 0) return -2;
   Aff A;
   for (int i = 0; i < 12; ++i) A.a[i] = affine_host12[i];
   const long n = (long)D * H * W;
