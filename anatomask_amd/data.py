@@ -10,6 +10,9 @@ reference's own loader (tests/golden/make_loader_fixtures.py imports it with a s
 The train transforms the drivers enable (SpatialTransform rotation / scaling, MirrorTransform; the intensity transforms are
 commented out in the reference, P/pretrain_AntoMask.py:99-109) run ON THE DEVICE (DeviceAugmenter -> csrc/aug_ops.hip); the host
 side only draws their parameters.  PrefetchLoader + DeviceFeed keep the GPU fed (pinned, double-buffered H2D on a copy stream).
+For supervised fine-tuning the segmentation follows the image through the same draws (get_training_transforms,
+P/pretrain_AntoMask.py:56-150): PairedDeviceFeed, PairedDeviceAugmenter (am_resample_labels), SupervisedFeed, and the host helpers
+region_lut / deep_supervision_targets.
 """
 import os
 import pickle
@@ -283,6 +286,81 @@ class DeviceAugmenter:
         return out
 
 
+# --------------------------------------------------------------------------- the segmentation half (supervised fine-tuning)
+def region_lut(regions, n_labels: int) -> torch.Tensor:
+    """int32 [n_labels]: bit r of entry c is set when label c belongs to regions[r] -- the table am_resample_labels turns into
+    ConvertSegmentationToRegionsTransform's channels (custom_transforms/region_based_training.py:23-38: channel r = isin(seg,
+    regions[r])).  An entry of `regions` is a label or a tuple / list of labels, as in the reference."""
+    regions = list(regions)
+    if len(regions) > 32:
+        raise ValueError(f"{len(regions)} regions: the label kernel packs a voxel's regions into one 32-bit word")
+    lut = np.zeros(int(n_labels), dtype=np.uint32)
+    for r, labels in enumerate(regions):
+        for c in (labels if isinstance(labels, (tuple, list)) else (labels,)):
+            if not 0 <= int(c) < n_labels:
+                raise ValueError(f"label {c} of region {r} is outside [0, {n_labels})")
+            lut[int(c)] |= np.uint32(1 << r)
+    return torch.from_numpy(lut.view(np.int32).copy())
+
+
+def deep_supervision_targets(target: torch.Tensor, scales) -> List[torch.Tensor]:
+    """DownsampleSegForDSTransform2(scales, order=0) (custom_transforms/deep_supervision_donwsampling.py) on a [B,C,D,H,W] target:
+    one tensor per scale, each a strided VIEW of `target` (nothing is copied; scale 1 is `target` itself).  A scale is a number or
+    one number per axis, 1 / f with an integer f that divides the extent; anything else raises NotImplementedError.
+    The reference resizes with batchgenerators' resize_segmentation = skimage.transform.resize(order=0, mode='edge',
+    anti_aliasing=False); for such a scale that is the sampling (o + 0.5) f - 0.5 rounded as scipy rounds it, i.e. the voxels
+    f//2, f//2 + f, ...  This is pinned to scipy.ndimage.zoom(order=0, mode='nearest', grid_mode=True) (tests/test_label_feed_cpu.py);
+    that skimage >= 0.19 takes this scipy path is from memory and has NOT been verified against skimage itself."""
+    if target.dim() != 5:
+        raise NotImplementedError(f"target of {target.dim()} dimensions: [B, C, D, H, W] is what is served")
+    out = []
+    for s in scales:
+        s3 = tuple(float(v) for v in s) if isinstance(s, (tuple, list)) else (float(s),) * 3
+        if len(s3) != 3 or any(v <= 0 for v in s3):
+            raise NotImplementedError(f"deep-supervision scale {s}")
+        f = [int(round(1.0 / v)) for v in s3]
+        if any(abs(f[d] * s3[d] - 1.0) > 1e-6 or target.shape[2 + d] % f[d] for d in range(3)):
+            raise NotImplementedError(f"deep-supervision scale {s} on extents {tuple(target.shape[2:])}: only 1 / f with f dividing the extent")
+        out.append(target if f == [1, 1, 1] else target[:, :, f[0] // 2::f[0], f[1] // 2::f[1], f[2] // 2::f[2]])
+    return out
+
+
+class PairedDeviceAugmenter:
+    """DeviceAugmenter for an image AND its segmentation (get_training_transforms, P/pretrain_AntoMask.py:56-150): one draw per sample
+    drives both halves.  (x_enl fp32, seg_enl int16, both (B,1,De,He,We) on the device) -> (data fp32 (B,1,D,H,W), target).  `data` is
+    what DeviceAugmenter(aug) returns for the same draws, bit for bit.  `target` follows through the same affines (am_resample_labels):
+    rotated / scaled samples by batchgenerators' label interpolation of order `order_seg` (border -1), the others as integer crops /
+    flips; then RemoveLabelTransform(*remove_label) and, with `regions`, ConvertSegmentationToRegionsTransform: int16 (B,1,D,H,W)
+    without regions, uint8 (B,R,D,H,W) with them (`n_labels` = size of the label table: labels >= n_labels belong to no region)."""
+
+    def __init__(self, aug: SpatialAugmenter, order_seg: int = 1, border_cval_seg: int = -1, remove_label=(-1, 0), regions=None,
+                 n_labels: Optional[int] = None):
+        if regions is not None and n_labels is None:
+            raise ValueError("regions need n_labels, the size of the label table")
+        self.aug, self.data_aug = aug, DeviceAugmenter(aug)
+        self.order_seg, self.cval, self.remove = int(order_seg), int(border_cval_seg), remove_label
+        self.n_regions = len(regions) if regions is not None else 0
+        self._lut_host = region_lut(regions, n_labels) if regions is not None else None
+        self._lut = None
+
+    def __call__(self, x_enl: torch.Tensor, seg_enl: torch.Tensor, params: Optional[List[dict]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        from . import ops
+        B = x_enl.shape[0]
+        assert seg_enl.dtype == torch.int16 and seg_enl.is_cuda and tuple(seg_enl.shape) == tuple(x_enl.shape) and seg_enl.shape[1] == 1
+        params = params if params is not None else [self.aug.draw() for _ in range(B)]
+        data = self.data_aug(x_enl, params)
+        R, dev = self.n_regions, seg_enl.device
+        if R and (self._lut is None or self._lut.device != dev):
+            self._lut = self._lut_host.to(dev)
+        target = torch.empty((B, R or 1, *self.aug.final), device=dev, dtype=torch.uint8 if R else torch.int16)
+        for b in range(B):
+            src = seg_enl[b, 0]
+            A = self.aug.affine(params[b], src.shape)
+            ops.resample_labels(src.contiguous(), None if R else target[b, 0], A.reshape(-1), self.order_seg if params[b]["modified"] else 0,
+                                self.cval, self.remove, self._lut if R else None, R, target[b] if R else None)
+        return data, target
+
+
 def gpu_numa_cpus(device_index: int) -> Optional[List[int]]:
     """CPUs of the NUMA node the GPU `device_index` hangs off (sysfs: /sys/bus/pci/devices/<bus id>/numa_node ->
     /sys/devices/system/node/node<N>/cpulist), or None when the platform does not say (single-node hosts report -1).
@@ -441,3 +519,103 @@ class DeviceFeed:
         self.k += 1
         self._start(self.k % self.depth, after=done)
         return out
+
+
+class PairedDeviceFeed(DeviceFeed):
+    """DeviceFeed for several tensors of a batch, by default the image and its segmentation: `next(feed)` is the tuple of device
+    tensors of `keys`.  Per slot one device buffer per key and one pinned staging buffer for every key that arrives un-pinned (the
+    loader's `seg` is pageable int16); the copies of a batch run on the copy stream behind the same `after` event and ONE ready event is
+    recorded after the last of them: the compute stream waits for it, and a pooled batch's `_release` is bound to it."""
+
+    def __init__(self, batches, device, keys: Sequence[str] = ("data", "seg"), depth: int = 2):
+        self.keys = tuple(keys)
+        super().__init__(batches, device, key=self.keys[0], depth=depth)
+
+    def _start(self, slot: int, after=None) -> bool:
+        self._reap(self.depth)                          # (see DeviceFeed._start)
+        try:
+            b = next(self.it)
+        except StopIteration:
+            self.ready[slot] = None
+            return False
+        hs = [b[k] for k in self.keys]
+        if self.dbuf[slot] is None or any(d.shape != h.shape or d.dtype != h.dtype for d, h in zip(self.dbuf[slot], hs)):
+            self.dbuf[slot] = tuple(torch.empty(h.shape, dtype=h.dtype, device=self.dev) for h in hs)
+        if self.pin[slot] is None:
+            self.pin[slot] = [None] * len(hs)
+        if self.ready[slot] is not None and not all(h.is_pinned() for h in hs):
+            self.ready[slot].synchronize()              # the previous copies out of this slot's staging buffers have finished
+        for i, h in enumerate(hs):
+            if not h.is_pinned():
+                p = self.pin[slot][i]
+                if p is None or p.shape != h.shape or p.dtype != h.dtype:
+                    p = self.pin[slot][i] = torch.empty(h.shape, dtype=h.dtype).pin_memory()
+                p.copy_(h)
+                hs[i] = p
+        with torch.cuda.stream(self.copy_stream):
+            if after is not None:
+                self.copy_stream.wait_event(after)
+            for d, h in zip(self.dbuf[slot], hs):
+                d.copy_(h, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self.copy_stream)
+        self.ready[slot] = ev
+        self._host_keepalive = hs
+        if "_release" in b:
+            self._pending.append((ev, b["_release"]))
+        return True
+
+    def close(self):
+        """wait for the copies in flight and hand their pool buffers back."""
+        self._reap(0)
+
+
+class SupervisedFeed:
+    """pretrain.Feed with the segmentation: loader threads -> pinned pool (image) + staging (labels) -> copy stream -> paired device
+    augmentation; next(feed) is (data fp32 (B,1,*input_size), target) as PairedDeviceAugmenter returns them -- what
+    get_training_transforms (P/pretrain_AntoMask.py:56-150) hands a supervised trainer, without deep supervision
+    (deep_supervision_targets makes the pyramid from `target`).  state() / load_state() as pretrain.Feed: torch tensors and python
+    scalars only, applied to the generators before the prefetch threads start."""
+
+    def __init__(self, folder, cases, batch, input_size, dev, rank, workers, augment: bool, seed: int, order_seg: int = 1, regions=None,
+                 n_labels: Optional[int] = None, state=None):
+        ds = PreprocessedDataset(folder, cases)
+        data0, seg0, _ = ds.load_case(ds.keys()[0])
+        if data0.shape[0] != 1 or seg0.shape[0] != 1:
+            raise NotImplementedError(f"{data0.shape[0]} image and {seg0.shape[0]} segmentation channels: one of each is what is served")
+        rot = ROTATION_FOR_DA
+        enl = tuple(int(v) for v in get_patch_size(tuple(input_size), rot, rot, rot, (0.85, 1.25))) if augment else tuple(input_size)
+        self.pool = PinnedPool((batch, 1, *enl), n=6 + 2 + workers)
+        self.loaders = {w: PatchLoader3D(ds, batch, enl, 0.33, seed=seed + 1000 * rank + w, final_patch_size=tuple(input_size), pool=self.pool)
+                        for w in range(workers)}
+        self.aug = PairedDeviceAugmenter(SpatialAugmenter(tuple(input_size), seed=seed + 77 + rank,
+                                                          p_rot=0.2 if augment else 0.0, p_scale=0.2 if augment else 0.0,
+                                                          mirror_axes=(0, 1, 2) if augment else ()),
+                                         order_seg=order_seg, regions=regions, n_labels=n_labels)
+        self.load_state(state)
+        cpus = gpu_numa_cpus(dev.index if getattr(dev, "index", None) is not None else 0) if getattr(dev, "type", "cpu") == "cuda" else None
+        self.pf = PrefetchLoader(lambda w: self.loaders[w], n_workers=workers, num_cached=6, cpus=cpus)
+        self.feed = PairedDeviceFeed(self.pf, dev)
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        return self.aug(*next(self.feed))
+
+    def state(self):
+        from .pretrain import rng_state_to_plain
+        return {"loader_rng": {int(w): rng_state_to_plain(ld.rng_snapshot()) for w, ld in self.loaders.items()},
+                "aug_rng": rng_state_to_plain(self.aug.aug.rs)}
+
+    def load_state(self, st):
+        from .pretrain import rng_state_from_plain
+        for w, s_ in (st or {}).get("loader_rng", {}).items():
+            if int(w) in self.loaders:
+                rng_state_from_plain(self.loaders[int(w)].rs, s_)
+        if st and "aug_rng" in st:
+            rng_state_from_plain(self.aug.aug.rs, st["aug_rng"])
+
+    def close(self):
+        self.pf.close()
+        self.feed.close()

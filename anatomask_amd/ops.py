@@ -688,6 +688,27 @@ def resample_affine(src: torch.Tensor, dst: torch.Tensor, affine_3x4, order: int
     return dst
 
 
+def resample_labels(src: torch.Tensor, dst: Optional[torch.Tensor], affine_3x4, order: int, cval: int = -1, remove=(-1, 0),
+                    region_bits: Optional[torch.Tensor] = None, n_regions: int = 0, regions_out: Optional[torch.Tensor] = None):
+    """The label half of resample_affine at the same coordinates: src int16 [Ds,Hs,Ws] -> dst int16 [D,H,W] (None: regions only) by
+    batchgenerators' label interpolation (order 1: the largest label whose trilinear mask value is >= 0.5, else 0; order 0: nearest,
+    outside -> cval), then remove[0] -> remove[1] (None: nothing removed).  region_bits int32 [n_lut] (data.region_lut) + regions_out
+    uint8 [n_regions,D,H,W]: one plane per region of the removed labels.  Returns (dst, regions_out)."""
+    assert src.dtype == torch.int16 and src.dim() == 3 and src.is_contiguous()
+    assert dst is not None or regions_out is not None
+    out_shape = tuple(dst.shape) if dst is not None else tuple(regions_out.shape[1:])
+    if dst is not None:
+        assert dst.dtype == torch.int16 and dst.dim() == 3 and dst.is_contiguous()
+    if regions_out is not None:
+        assert region_bits is not None and region_bits.dtype == torch.int32 and region_bits.dim() == 1 and region_bits.is_contiguous()
+        assert regions_out.dtype == torch.uint8 and regions_out.is_contiguous() and tuple(regions_out.shape) == (int(n_regions), *out_shape)
+    rm_from, rm_to = (int(v) for v in remove) if remove is not None else (0, 0)
+    arr = (_ct.c_float * 12)(*[float(v) for v in affine_3x4])
+    hip.lib().resample_labels(src.data_ptr(), *src.shape, _p(dst), *out_shape, _ct.addressof(arr), int(order), int(cval), rm_from, rm_to,
+                              _p(region_bits), 0 if region_bits is None else region_bits.numel(), int(n_regions), _p(regions_out), _stream())
+    return dst, regions_out
+
+
 # ------------------------------------------------------------------ segmentation inference (seg_ops.hip)
 SEG_LDS_C = 240   # AM_SEG_LDS_C
 

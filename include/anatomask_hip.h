@@ -317,6 +317,24 @@ int am_guard_restore(void* dst, const void* snapshot, long nbytes, const int* gu
 int am_spline_prefilter(float* vol, int D, int H, int W, void* stream);
 int am_resample_affine(const float* src, int Ds, int Hs, int Ws, float* dst, int D, int H, int W, const float* affine_host12, int order,
                        float cval, void* stream);
+/* The segmentation half of the same transforms, for supervised fine-tuning (get_training_transforms, P/pretrain_AntoMask.py:56-150):
+ * SpatialTransform(border_mode_seg='constant', border_cval_seg=-1, order_seg=1) (:80-91) + MirrorTransform (:111-112) through the SAME
+ * affine, RemoveLabelTransform(-1, 0) (:118) and, optionally, ConvertSegmentationToRegionsTransform (:139-143;
+ * custom_transforms/region_based_training.py:23-38) in one pass.  src / dst: int16 [D][H][W] device buffers of ONE sample.  The source
+ * coordinate of an output voxel is the fp32 value am_resample_affine computes for it, inside = 0 <= p <= n-1 on every axis.
+ * order 0: the label at floor(p + 0.5) (clamped to n-1), outside -> cval: an integer affine is an exact crop / flip.
+ * order 1: batchgenerators' interpolate_img(is_seg=True): every label's mask is interpolated trilinearly and the LARGEST label whose
+ *   value is >= 0.5 wins, 0 when none is -- here as the sums of the 8 trilinear corner weights (the +1 index clamped to n-1) per
+ *   label, accumulated in corner order; -1 takes part like any label; outside -> 0 (every mask interpolates to -1 there), not cval.
+ * Then label == remove_from -> remove_to (equal: no-op) and dst is written.  With region_bits, regions_out[r][voxel] =
+ * (bits >> r) & 1 for r < n_regions, bits = region_bits[label] for 0 <= label < n_lut and 0 otherwise (uint8 where the reference keeps
+ * the segmentation's dtype).  -2, and no launch, for a null src / affine_host12, both outputs null, a non-positive extent, an order
+ * other than 0 / 1, regions_out without region_bits or with n_regions outside 1..32. */
+int am_resample_labels(const int16_t* src, int Ds, int Hs, int Ws, int16_t* dst /* may be NULL when regions_out is given */,
+                       int D, int H, int W, const float* affine_host12, int order /* 0 | 1 */, int cval /* order 0 only */,
+                       int remove_from, int remove_to /* applied after interpolation; equal = no-op */,
+                       const int32_t* region_bits /* NULL, or device int32 [n_lut]: bit r set when the label belongs to region r */,
+                       int n_lut, int n_regions /* <= 32 */, uint8_t* regions_out /* NULL or [n_regions][D][H][W] */, void* stream);
 
 /* ---- sparse layer zoo of the SparK encoder for other backbones (P/encoder3D.py = nnunetv2/training/nnUNetTrainer/
  * variants/pretrain/encoder3D.py).  Same tensors as above: channels-last [B][D][H][W][C] + uint8 patch mask (fd, fh, fw) + block shift;
