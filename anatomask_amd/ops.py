@@ -816,3 +816,87 @@ def seg_export(acc: torch.Tensor, wsum: torch.Tensor, crop_start, crop_size, non
                          SEG_SIGMOID if order is not None else SEG_SOFTMAX, _p(order_t), _p(probs), _p(labels),
                          labels.element_size() if labels is not None else 1, _stream())
     return probs, labels
+
+
+# ------------------------------------------------------------------ segmentation loss (loss_ops.hip)
+SEG_LOSS_TILE = 256   # AM_SEG_LOSS_TILE
+
+
+def _seg_loss_geometry(mode: int, logits: torch.Tensor, target: torch.Tensor, has_ignore: bool):
+    """validate (logits fp32 [B,K,D,H,W] contiguous on the GPU; target int16 [B,1,D,H,W] (softmax) or uint8 / bool [B,K(+1),D,H,W]
+    (sigmoid), any strides, same device) -> (B, K, D, H, W, the target's element strides)."""
+    if mode not in (SEG_SOFTMAX, SEG_SIGMOID):
+        raise ValueError(f"mode {mode}: SEG_SOFTMAX or SEG_SIGMOID")
+    if not logits.is_cuda:
+        raise RuntimeError("the segmentation loss runs on the GPU only (no CPU path exists)")
+    if logits.dtype != torch.float32 or logits.dim() != 5 or not logits.is_contiguous():
+        raise ValueError(f"logits must be contiguous fp32 [B,K,D,H,W], got {logits.dtype} {tuple(logits.shape)} contiguous={logits.is_contiguous()}")
+    if target.device != logits.device:
+        raise RuntimeError(f"target on {target.device}, logits on {logits.device}")
+    B, K, D, H, W = logits.shape
+    want_c = 1 if mode == SEG_SOFTMAX else K + (1 if has_ignore else 0)
+    if target.dim() != 5 or tuple(target.shape) != (B, want_c, D, H, W):
+        raise ValueError(f"target {tuple(target.shape)} does not match logits {tuple(logits.shape)}: expected {(B, want_c, D, H, W)}")
+    if mode == SEG_SOFTMAX:
+        if target.dtype != torch.int16:
+            raise TypeError(f"softmax mode reads int16 labels, got {target.dtype}")
+        if K < 2 or K > 32767:
+            raise ValueError(f"K = {K}: 2 .. 32767 classes")
+    elif target.dtype not in (torch.uint8, torch.bool):
+        raise TypeError(f"sigmoid mode reads uint8 / bool region channels, got {target.dtype}")
+    return B, K, D, H, W, tuple(int(s) for s in target.stride())
+
+
+def seg_loss_sums(mode: int, logits: torch.Tensor, target: torch.Tensor, ignore_label: Optional[int] = None, keep_lse: bool = True):
+    """Pass 1 of the fused Dice + CE / BCE loss: (sums fp64 [B,K+1,4], lse fp32 [B,D*H*W,2] or None: per voxel the maximum and the log of the
+    rescaled sum, whose sum is the log-sum-exp -- kept apart so that x - max stays exact under large shifted logits).  sums[b,k] = (sum p y m, sum p m,
+    sum y m, CE / BCE numerator of class k), sums[b,K] = (unmasked voxels, CE part of voxels of no class, 0, 0).  softmax: ignore_label
+    (None: none) masks voxels; sigmoid: ignore_label is not None says that the target's last channel is the ignore mask.  The target is
+    read through its strides (a deep-supervision view is consumed as it is)."""
+    has_ignore = ignore_label is not None
+    B, K, D, H, W, ts = _seg_loss_geometry(mode, logits, target, has_ignore)
+    N = D * H * W
+    rows = (N + SEG_LOSS_TILE - 1) // SEG_LOSS_TILE
+    partials = torch.empty(B * rows * (K + 1) * 4, device=logits.device, dtype=torch.float32)
+    sums = torch.empty(B, K + 1, 4, device=logits.device, dtype=torch.float64)
+    lse = torch.empty(B, N, 2, device=logits.device, dtype=torch.float32) if (keep_lse and mode == SEG_SOFTMAX) else None
+    hip.lib().seg_loss_sums(mode, logits.data_ptr(), B, K, D, H, W, target.data_ptr(), *ts, int(has_ignore),
+                            int(ignore_label) if (has_ignore and mode == SEG_SOFTMAX) else 0, partials.data_ptr(), sums.data_ptr(), _p(lse), _stream())
+    return sums, lse
+
+
+def seg_loss_coeffs(mode: int, sums: torch.Tensor, n_voxels: int, batch_dice: bool, do_bg: bool, has_ignore: bool, smooth: float,
+                    weight_dice: float, weight_ce: float, level_weight: float = 1.0, loss_total: Optional[torch.Tensor] = None):
+    """The sums table -> (coef fp32 [2*B*K + 1], loss fp32 [1]) on the device, no read-back: coef = w_dice (a_c, b_c) per (sample, class)
+    and, last, w_ce / n.  loss_total fp32 [1] (optional) += level_weight * loss."""
+    assert sums.dtype == torch.float64 and sums.dim() == 3 and sums.shape[2] == 4 and sums.is_contiguous()
+    B, K = sums.shape[0], sums.shape[1] - 1
+    if not do_bg and K < 2:
+        raise ValueError("do_bg=False leaves no class to average")
+    coef = torch.empty(2 * B * K + 1, device=sums.device, dtype=torch.float32)
+    loss = torch.empty(1, device=sums.device, dtype=torch.float32)
+    if loss_total is not None:
+        assert loss_total.dtype == torch.float32 and loss_total.numel() == 1 and loss_total.device == sums.device
+    hip.lib().seg_loss_coeffs(mode, sums.data_ptr(), B, K, int(n_voxels), int(bool(batch_dice)), int(bool(do_bg)), int(bool(has_ignore)),
+                              float(smooth), float(weight_dice), float(weight_ce), float(level_weight), coef.data_ptr(), loss.data_ptr(),
+                              _p(loss_total), _stream())
+    return coef, loss
+
+
+def seg_loss_grad(mode: int, logits: torch.Tensor, target: torch.Tensor, ignore_label: Optional[int], lse: Optional[torch.Tensor],
+                  coef: torch.Tensor, gscale: torch.Tensor, weight: float = 1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Pass 2: dlogits fp32 [B,K,D,H,W] = gscale * weight * d loss / d logits; gscale is a one-element fp32 DEVICE tensor (the upstream
+    gradient is never read back)."""
+    has_ignore = ignore_label is not None
+    B, K, D, H, W, ts = _seg_loss_geometry(mode, logits, target, has_ignore)
+    assert coef.dtype == torch.float32 and coef.numel() == 2 * B * K + 1 and coef.is_contiguous() and coef.device == logits.device
+    assert gscale.dtype == torch.float32 and gscale.numel() == 1 and gscale.device == logits.device
+    if mode == SEG_SOFTMAX:
+        assert lse is not None and lse.dtype == torch.float32 and lse.numel() == 2 * B * D * H * W and lse.is_contiguous()
+    if out is None:
+        out = torch.empty_like(logits)
+    assert out.dtype == torch.float32 and tuple(out.shape) == tuple(logits.shape) and out.is_contiguous() and out.device == logits.device
+    hip.lib().seg_loss_grad(mode, logits.data_ptr(), B, K, D, H, W, target.data_ptr(), *ts, int(has_ignore),
+                            int(ignore_label) if (has_ignore and mode == SEG_SOFTMAX) else 0, _p(lse), coef.data_ptr(), gscale.data_ptr(),
+                            float(weight), out.data_ptr(), _stream())
+    return out

@@ -444,6 +444,41 @@ int am_seg_finalize(const float* acc, const float* wsum, int K, int Xp, int Yp, 
 int am_seg_export(const float* acc, const float* wsum, int K, int Xp, int Yp, int Zp, int c0, int c1, int c2, int X, int Y, int Z, int nonlin,
                   const int32_t* region_order, float* probs, void* labels, int label_bytes, void* stream);
 
+/* ---- segmentation loss: Dice + CE (AM_SEG_SOFTMAX) / Dice + BCE (AM_SEG_SIGMOID) with the logit gradient (loss_ops.hip) ----
+ * DC_and_CE_loss / DC_and_BCE_loss around MemoryEfficientSoftDiceLoss (nnunetv2/training/loss/compound_losses.py:8-100, dice.py:58-116,
+ * robust_ce_loss.py:6-16) as nnUNetTrainer._build_loss composes them (nnUNetTrainer.py:342-365).
+ * logits fp32 [B][K][D][H][W] contiguous.  target, read through ELEMENT strides (tsb, tsc, tsd, tsh, tsw) of b, c, d, h, w:
+ *   AM_SEG_SOFTMAX: int16 labels [B][1][D][H][W]; has_ignore: voxels of ignore_label are masked (compound_losses.py:38-46).  A label outside
+ *                   [0, K) that is not the ignore label belongs to no class (y = 0 in every class, CE = log-sum-exp; the reference's
+ *                   scatter_ errors there, dice.py:94) and indexes nothing.
+ *   AM_SEG_SIGMOID: uint8 region channels [B][K (+ 1)][D][H][W], nonzero = set; has_ignore: channel K is the ignore mask (:85-89).
+ * am_seg_loss_sums: one sweep of the logits -> partials fp32 [B][rows][K + 1][4], rows = ceil(D H W / AM_SEG_LOSS_TILE), entry k < K =
+ *   {sum p y m, sum p m, sum y m, sum of the CE / BCE terms of class k}, entry K = {unmasked voxels, sum of m lse over voxels of no class,
+ *   0, 0} (dice.py:98-101); the rows are then added in a fixed order in fp64 -> sums [B][K + 1][4].  No atomics: the same input gives the
+ *   same bits.  lse fp32 [B][D H W][2] (softmax; NULL: not kept, no gradient pass can follow): per voxel (max_k x_k, log sum_k exp(x_k - max)),
+ *   whose sum is the log-sum-exp; kept apart so that p = exp((x - max) - log sum) loses nothing to the magnitude of the logits.  partials and
+ *   sums 16-byte aligned, lse 8-byte. */
+#define AM_SEG_LOSS_TILE 256
+int am_seg_loss_sums(int mode, const float* logits, int B, int K, int D, int H, int W, const void* target, long tsb, long tsc, long tsd,
+                     long tsh, long tsw, int has_ignore, int ignore_label, float* partials, double* sums, float* lse, void* stream);
+/* sums -> the loss and the coefficients of its gradient, on the device (dice.py:108-116, compound_losses.py:51-57,94-100):
+ *   dice = -mean_c (2 I_c + smooth) / max(G_c + P_c + smooth, 1e-8) over C' terms: the classes from 1 (do_bg = 0) or 0, per sample unless
+ *   batch_dice; ce = CE numerator / n with n = unmasked voxels (softmax: 0 when none is left, as the reference skips the term),
+ *   B K N (sigmoid), max(unmasked voxels, 1e-8) (sigmoid with the ignore channel); loss = w_ce ce + w_dice dice.
+ *   coef fp32 [B][K][2] = w_dice (a_c, b_c), a_c = -2 / (C' den_c), b_c = num_c / (C' den_c^2) (0 for a class that is not averaged; b_c = 0
+ *   where the clip holds the denominator), and coef[2 B K] = w_ce / n.  loss_level[0] = loss; loss_total (or NULL)[0] += level_weight * loss
+ *   (deep_supervision.py:30-34: the levels run in stream order). */
+int am_seg_loss_coeffs(int mode, const double* sums, int B, int K, long N, int batch_dice, int do_bg, int has_ignore, double smooth,
+                       double w_dice, double w_ce, float level_weight, float* coef, float* loss_level, float* loss_total, void* stream);
+/* dlogits fp32 [B][K][D][H][W] = s * d loss / d logits with s = gscale[0] * weight (gscale on the device: the upstream gradient), g_k =
+ * a_k y_k + b_k, c = coef[2 B K]:
+ *   softmax: s m (p_k (g_k - sum_j p_j g_j) + c (p_k - y_k))        sigmoid: s m (p_k (1 - p_k) g_k + c (p_k - y_k))
+ * (the derivatives of dice.py:100-116 and of torch's cross_entropy / binary_cross_entropy_with_logits means).  lse: what am_seg_loss_sums
+ * kept (softmax). */
+int am_seg_loss_grad(int mode, const float* logits, int B, int K, int D, int H, int W, const void* target, long tsb, long tsc, long tsd,
+                     long tsh, long tsw, int has_ignore, int ignore_label, const float* lse, const float* coef, const float* gscale,
+                     float weight, float* dlogits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
