@@ -215,11 +215,18 @@ __global__ void ema_kernel(float* __restrict__ ema, const float* __restrict__ p,
 }
 
 // timm's update on an integer state_dict entry (BatchNorm's num_batches_tracked): ema.copy_(ema * decay + (1 - decay) * model) --
-// int64 * python float promotes to float32, the sum is float32, copy_ into int64 truncates toward zero
+// int64 * python float promotes to float32, the sum is float32, copy_ into int64 truncates toward zero.  torch rounds each product and
+// then the sum; a product fused into the sum (what the compiler makes of the one-line form) truncates to another integer in a fifth of
+// the counters below 4096 at decay 0.9999, so contraction is off here and the three operations are spelled out.
 __global__ void ema_i64_kernel(long long* __restrict__ ema, const long long* __restrict__ p, int n, float decay, float one_minus, const int* __restrict__ guard) {
+#pragma clang fp contract(off)
   if (guard && guard[0]) return;
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) ema[i] = (long long)((float)ema[i] * decay + one_minus * (float)p[i]);
+  if (i < n) {
+    const float a = (float)ema[i] * decay, b = one_minus * (float)p[i];
+    const float s = a + b;
+    ema[i] = (long long)s;
+  }
 }
 
 // guard latched: put the snapshot taken before the step back (BatchNorm running statistics / counters the student's forward updated)
