@@ -55,12 +55,13 @@ inline VoxGeo mkvox(int B, int D, int H, int W, int C, const int* plist, int n_a
 }
 
 // sum of `val` over the L consecutive threads of a segment (pos = index inside the segment), fixed tree order: deterministic.
-// Every thread of the workgroup calls it (L is uniform); sm holds 256 floats.
+// Every thread of the workgroup calls it (L is uniform); sm holds 256 floats.  When the chunks per voxel do not divide 256 the last
+// lanes hold no voxel and form a cut-off segment (their result is discarded): tid + s < 256 keeps their reads inside sm.
 __device__ __forceinline__ float seg_sum(float* sm, int tid, int pos, int L, int P2, float val) {
   sm[tid] = val;
   __syncthreads();
   for (int s = P2 >> 1; s > 0; s >>= 1) {
-    if (pos < s && pos + s < L) sm[tid] += sm[tid + s];
+    if (pos < s && pos + s < L && tid + s < 256) sm[tid] += sm[tid + s];
     __syncthreads();
   }
   const float r = sm[tid - pos];

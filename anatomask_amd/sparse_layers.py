@@ -115,6 +115,11 @@ class _VoxelNormFn(torch.autograd.Function):
         B, D, H, W, C = x_cl.shape
         bs = _bshift(mi, D)
         _check_list(mi)
+        epc = 16 // x_cl.element_size()                  # channels per 16-byte chunk: a group is whole chunks, or a whole number of groups fills one
+        cg = C if kind == 1 else C // max(groups, 1)
+        if kind != 1 and (groups < 1 or C % groups or not (cg % epc == 0 or epc % cg == 0)):
+            raise NotImplementedError(f"per-voxel norm: {C} channels in {groups} groups = {cg} channels per group, which neither fills nor "
+                                      f"divides the {epc}-channel chunk of {x_cl.dtype} (no kernel for that split)")
         y = torch.zeros_like(x_cl)
         g32, b32 = gamma.float().contiguous().view(-1), (beta.float().contiguous().view(-1) if beta is not None else None)
         _lib().voxel_norm_fwd(ops._dt(x_cl), kind, x_cl.data_ptr(), y.data_ptr(), B, D, H, W, C, groups, g32.data_ptr(), ops._p(b32), float(eps),
