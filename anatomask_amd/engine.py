@@ -243,8 +243,9 @@ def _enc_block(W, pk, inp, mask, counts, sp, s: int, b: int, x, keep: bool = Tru
     first = b == 0
     if stride is None or not first:
         stride = 2 if (first and s > 0) else 1
-    rec_ = {"p": p, "s": s, "b": b, "first": first, "stride": stride, "x": x}
-    if s == 0 and first and prefix is None:
+    stem = s == 0 and first and prefix is None
+    rec_ = {"p": p, "s": s, "b": b, "first": first, "stride": stride, "x": x, "bs": bs, "stem": stem}
+    if stem:
         y1, pt1 = ops.stem_conv_fwd(inp, W[f"{p}.conv1.weight"], W[f"{p}.conv1.bias"], mask, bs, dt, want_partials=True)
     else:
         y1, pt1 = ops.conv3d(CONV_FWD, x, pk.get(W, f"{p}.conv1.weight", False, False), W[f"{p}.conv1.bias"], sp, 3, stride,
@@ -260,7 +261,7 @@ def _enc_block(W, pk, inp, mask, counts, sp, s: int, b: int, x, keep: bool = Tru
         y2, pt2 = ops.conv3d(CONV_FWD, a1, w2, W[f"{p}.conv2.bias"], sp, 3, 1,
                              in_mask=mask, in_bshift=bs, out_mask=mask, out_bshift=bs, want_partials=True)
     st2 = _sparse_norm(y2, mask, bs, counts, W[f"{p}.norm2.weight"], W[f"{p}.norm2.bias"], 1e-5, pt2)
-    if s == 0 and first and prefix is None:      # 1x1 Cin=1 shortcut folded into the apply pass
+    if stem:                                     # 1x1 Cin=1 shortcut folded into the apply pass
         out = ops.norm_apply(y2, st2, ACT_LRELU, mask, bs, stem=(inp, W[f"{p}.conv3.weight"].view(-1), W[f"{p}.conv3.bias"]))
     elif first:
         sc = ops.conv3d(CONV_FWD, x, pk.get(W, f"{p}.conv3.weight", False, False), W[f"{p}.conv3.bias"], sp, 1, stride,
@@ -585,9 +586,11 @@ def _enc_block_backward(W, G, pk: PackCache, inp: torch.Tensor, mask: MaskInfo, 
                         free_saved: bool = False) -> Optional[torch.Tensor]:
     """backward of ONE BasicResBlock (`_enc_block`'s record t): gout = gradient wrt the block output (active voxels only); accumulates
     the block's parameter gradients into G; returns the gradient wrt the block INPUT (None for the Cin = 1 stem block).
-    base: first block of a stage -- the gradient the block input already has from its densify branch (accumulated into, and returned), or None."""
+    base: first block of a stage -- the gradient the block input already has from its densify branch (accumulated into, and returned), or None.
+    The block shift and whether the block is the stem come from the record: a localization block of the segmentation network at s = 0 is
+    no stem, and its stride-1 stage 5 runs at stage 4's grid."""
     p, s = t["p"], t["s"]
-    bs = 4 - s
+    bs = t["bs"]
     y2, a1, y1, out, x = t["y2"], t["a1"], t["y1"], t["out"], t["x"]
     dpre = torch.empty_like(y2)                      # gradient of the shortcut branch
     # conv2.bias gradient = sum of dy2 (folded into the apply pass); conv3.bias gradient = sum of dpre = norm2's dbeta
@@ -602,7 +605,7 @@ def _enc_block_backward(W, G, pk: PackCache, inp: torch.Tensor, mask: MaskInfo, 
     dy1 = ops.norm_backward(da1, None, y1, t["st1"], W[f"{p}.norm1.weight"], ACT_LRELU, mask, bs,
                             G[f"{p}.norm1.weight"], G[f"{p}.norm1.bias"], dxsum=G[f"{p}.conv1.bias"], reduced=red1)
     stride = t["stride"]
-    if s == 0 and t["first"]:                        # Cin = 1 stem: weight/bias gradients only
+    if t["stem"]:                                    # Cin = 1 stem: weight/bias gradients only
         ops.stem_conv_wgrad(inp, dy1, 3, mask, bs, G[f"{p}.conv1.weight"].view(-1, 27), None, deterministic=pk.deterministic)
         ops.stem_conv_wgrad(inp, dpre, 1, mask, bs, G[f"{p}.conv3.weight"].view(-1, 1), None, deterministic=pk.deterministic)
         return None
@@ -680,7 +683,7 @@ def backward(spec: Spec, W: Dict[str, torch.Tensor], G: Dict[str, torch.Tensor],
         _join_side(inp.device)            # (also when backward raises: the kept activations must not outlive the call)
 
 
-# ====================================================================================== segmentation network (inference only)
+# ====================================================================================== segmentation network
 NET = ENC.rsplit(".", 1)[0]            # the STUNet's own parameter names live under this prefix in W (as a stand-alone STUNet's do)
 
 
@@ -690,10 +693,12 @@ def _dense_mask(size: Tuple[int, int, int], device) -> MaskInfo:
     return MaskInfo(torch.ones(1, *f, dtype=torch.uint8, device=device), n_active=f[0] * f[1] * f[2])
 
 
-def seg_encoder_forward(W, pk: PackCache, inp: torch.Tensor, depth: Sequence[int], mask: Optional[MaskInfo] = None, counts=None) -> List[torch.Tensor]:
+def seg_encoder_forward(W, pk: PackCache, inp: torch.Tensor, depth: Sequence[int], mask: Optional[MaskInfo] = None, counts=None,
+                        recs: Optional[List[List[dict]]] = None) -> List[torch.Tensor]:
     """conv_blocks_context of P/STUNet.py:35-46,72-77 on ONE sample (inp fp32 [1,D,H,W]): the 6 stage maps, channels-last, dense.
     Stages 0-4 are the pretraining encoder's blocks on an all-active mask; stage 5 is a stride-1 first block with a 1x1 shortcut
-    (pool [1,1,1]) at stage 4's grid.  nn.InstanceNorm3d normalises per sample, hence one sample per call."""
+    (pool [1,1,1]) at stage 4's grid.  nn.InstanceNorm3d normalises per sample, hence one sample per call.
+    recs (a list): receives the stages' block records (kept activations) for seg_backward."""
     size = tuple(inp.shape[1:])
     if mask is None:
         mask = _dense_mask(size, inp.device)
@@ -701,24 +706,35 @@ def seg_encoder_forward(W, pk: PackCache, inp: torch.Tensor, depth: Sequence[int
     feats, x = [], None
     for s in range(6):
         sp = tuple(v >> min(s, 4) for v in size)
+        stage = []
         for b in range(depth[s]):
-            x, _ = _enc_block(W, pk, inp, mask, counts, sp, s, b, x, keep=False, stride=1 if s == 5 else None)
+            x, r_ = _enc_block(W, pk, inp, mask, counts, sp, s, b, x, keep=recs is not None, stride=1 if s == 5 else None)
+            if recs is not None:
+                stage.append(r_)
+        if recs is not None:
+            recs.append(stage)
         feats.append(x)
     return feats
 
 
-def seg_forward(W, pk: PackCache, inp: torch.Tensor, depth: Sequence[int], all_levels: bool = False) -> List[torch.Tensor]:
-    """P/STUNet.py:70-93 without the heads, forward only (no tape): inp fp32 [B,D,H,W] -> the decoder's output features channels-last
+def seg_forward(W, pk: PackCache, inp: torch.Tensor, depth: Sequence[int], all_levels: bool = False,
+                tape: Optional[List[dict]] = None) -> List[torch.Tensor]:
+    """P/STUNet.py:70-93 without the heads: inp fp32 [B,D,H,W] -> the decoder's output features channels-last
     [B,D',H',W',C] in the compute dtype, of the last level only or (all_levels) of levels 0..4 (coarse -> fine).
     Per decoder level u: Upsample_Layer_nearest's 1x1 conv at the COARSE grid (it commutes with nearest upsampling: 1/8 of the work at
     factor 2) -> am_seg_upcat (upsample into the first half of torch.cat((x, skip), 1)) -> BasicResBlock(s) 2C -> C with a 1x1 shortcut.
-    Samples run one at a time (per-sample InstanceNorm statistics) into batch-shaped outputs."""
+    Samples run one at a time (per-sample InstanceNorm statistics) into batch-shaped outputs.
+    tape (a list): one dict per sample is appended with what seg_backward needs -- the block records of the encoder stages ('enc') and
+    of the localization blocks ('loc'), the inputs of the upsample convs ('up') and the mask / counts.  The level features are the
+    returned tensors.  A loss may couple the samples (batch Dice), so the tapes of ALL samples live until the backward."""
     B = inp.shape[0]
     outs: List[Optional[torch.Tensor]] = [None] * 5
     mask = _dense_mask(tuple(inp.shape[1:]), inp.device)
     counts = _counts(mask, range(5))
+    keep = tape is not None
     for bi in range(B):
-        feats = seg_encoder_forward(W, pk, inp[bi:bi + 1], depth, mask, counts)
+        t = {"enc": [], "loc": [], "up": [], "mask": mask, "counts": counts} if keep else None
+        feats = seg_encoder_forward(W, pk, inp[bi:bi + 1], depth, mask, counts, t["enc"] if keep else None)
         x = feats[5]
         for u in range(5):
             s = 4 - u
@@ -726,13 +742,61 @@ def seg_forward(W, pk: PackCache, inp: torch.Tensor, depth: Sequence[int], all_l
             sp = tuple(skip.shape[1:4])
             wn = f"{NET}.upsample_layers.{u}.conv.weight"
             xu = ops.conv3d(CONV_FWD, x, pk.get(W, wn, False, False), W[f"{NET}.upsample_layers.{u}.conv.bias"], tuple(x.shape[1:4]), 1, 1)
+            if keep:
+                t["up"].append(x)
+                t["loc"].append([])
             x = ops.seg_upcat(xu, skip)
             for b in range(depth[s]):
-                x, _ = _enc_block(W, pk, None, mask, counts, sp, s, b, x, keep=False, stride=1, prefix=f"{NET}.conv_blocks_localization.{u}")
+                x, r_ = _enc_block(W, pk, None, mask, counts, sp, s, b, x, keep=keep, stride=1, prefix=f"{NET}.conv_blocks_localization.{u}")
+                if keep:
+                    t["loc"][u].append(r_)
             if (all_levels or u == 4) and B == 1:
                 outs[u] = x
             elif all_levels or u == 4:
                 if outs[u] is None:
                     outs[u] = torch.empty(B, *x.shape[1:], device=x.device, dtype=x.dtype)
                 outs[u][bi:bi + 1].copy_(x)
+        if keep:
+            tape.append(t)
     return outs if all_levels else [outs[4]]
+
+
+def seg_backward(W, G, pk: PackCache, inp: torch.Tensor, depth: Sequence[int], tape: dict, dfeat: Sequence[Optional[torch.Tensor]]):
+    """backward of seg_forward for ONE sample: inp fp32 [1,D,H,W], tape = that sample's entry of seg_forward's tape, dfeat[u] = the
+    gradient wrt level u's features [1,D',H',W',C] in the compute dtype (what am_seg_head_bwd leaves; it is accumulated into) or None.
+    Accumulates every parameter gradient below the heads into G (fp32, torch layout, names under NET).
+    Samples run one at a time because the InstanceNorm statistics are per sample; they accumulate into one G.  A batch loss (batch Dice)
+    couples the samples, so every sample's forward must have run -- and its tape be kept -- before the first backward.
+    Fine -> coarse, per level u: the localization blocks (_enc_block_backward) -> am_seg_upcat_bwd -> the upsample conv's bias
+    (chan_sum), weight (conv3d_wgrad k1) and data gradient (CONV_DGRAD k1, added onto dfeat[u - 1]); dskip becomes the gradient of
+    encoder stage 4 - u, onto which the first block of stage 5 - u later adds its own (`base`).  Then stages 5 .. 0 with the stem."""
+    mask = tape["mask"]
+    gstage: List[Optional[torch.Tensor]] = [None] * 6
+    g = None                                          # gradient wrt level u's features arriving from level u + 1 (dfeat[u] included)
+    try:
+        for u in reversed(range(5)):
+            if g is None:
+                g = dfeat[u]
+            if g is None:
+                g = torch.zeros_like(tape["loc"][u][-1]["out"])
+            for t in reversed(tape["loc"][u]):
+                g = _enc_block_backward(W, G, pk, None, mask, t, g, None)
+            xin = tape["up"][u]                       # the upsample conv's input: stage 5's map (u = 0) or level u - 1's features
+            du, gstage[4 - u] = ops.seg_upcat_bwd(g, g.shape[1] // xin.shape[1])
+            wn = f"{NET}.upsample_layers.{u}.conv.weight"
+            ops.chan_sum(du, None, 0, G[f"{NET}.upsample_layers.{u}.conv.bias"])
+            _wgrad_into(pk, G, wn, CONV_FWD, xin, du, 1, 1)
+            into = dfeat[u - 1] if u > 0 else None
+            g = ops.conv3d(CONV_DGRAD, du, pk.get(W, wn, False, True), None, tuple(xin.shape[1:4]), 1, 1, out=into, accumulate=into is not None)
+        gstage[5] = g
+        for s in reversed(range(6)):
+            gout = gstage[s]
+            for t in reversed(tape["enc"][s]):
+                first = t["first"] and s > 0
+                gx = _enc_block_backward(W, G, pk, inp, mask, t, gout, gstage[s - 1] if first else None)
+                if first:
+                    gstage[s - 1] = gx
+                elif gx is not None:
+                    gout = gx
+    finally:
+        _join_side(inp.device)

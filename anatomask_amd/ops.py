@@ -818,6 +818,51 @@ def seg_export(acc: torch.Tensor, wsum: torch.Tensor, crop_start, crop_size, non
     return probs, labels
 
 
+# ------------------------------------------------------------------ segmentation fine-tuning (seg_bwd_ops.hip)
+SEG_HEAD_BWD_TILE, SEG_HEAD_BWD_SLOTS = 64, 1024   # AM_SEG_HEAD_BWD_TILE / AM_SEG_HEAD_BWD_SLOTS
+
+
+def seg_head_bwd_workspace_floats(B: int, n_voxels: int, C: int, K: int) -> int:
+    """floats of am_seg_head_bwd's workspace: one slot (partial dw, db) per workgroup of its persistent grid."""
+    slots = min(B * ((n_voxels + SEG_HEAD_BWD_TILE - 1) // SEG_HEAD_BWD_TILE), SEG_HEAD_BWD_SLOTS)
+    return slots * (K * C + K)
+
+
+def seg_head_bwd(dlogits: torch.Tensor, f: torch.Tensor, w: torch.Tensor, dw_accum: torch.Tensor, db_accum: torch.Tensor,
+                 df: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
+    """backward of seg_head in one pass over dlogits fp32 [B,K,D,H,W]: returns df [B,D,H,W,C] (f's dtype; accumulate: added to the given
+    df, one rounding) and adds the weight / bias gradients to dw_accum fp32 (K,C[,1,1,1]) / db_accum fp32 [K].  No atomics: two calls on
+    the same input give the same bits."""
+    B, D, H, W, Cc = f.shape
+    K = w.shape[0]
+    assert dlogits.dtype == torch.float32 and tuple(dlogits.shape) == (B, K, D, H, W) and dlogits.is_contiguous() and f.is_contiguous()
+    assert w.dtype == torch.float32 and w.numel() == K * Cc and w.is_contiguous()
+    assert dw_accum.dtype == torch.float32 and dw_accum.numel() == K * Cc and dw_accum.is_contiguous()
+    assert db_accum.dtype == torch.float32 and db_accum.numel() == K and db_accum.is_contiguous()
+    if df is None:
+        assert not accumulate, "accumulate needs the df to add to"
+        df = torch.empty_like(f)
+    assert df.dtype == f.dtype and tuple(df.shape) == tuple(f.shape) and df.is_contiguous()
+    ws = torch.empty(seg_head_bwd_workspace_floats(B, D * H * W, Cc, K), device=f.device, dtype=torch.float32)
+    hip.lib().seg_head_bwd(_dt(f), dlogits.data_ptr(), f.data_ptr(), w.data_ptr(), B, D, H, W, Cc, K, df.data_ptr(), int(bool(accumulate)),
+                           dw_accum.data_ptr(), db_accum.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    return df
+
+
+def seg_upcat_bwd(dy: torch.Tensor, factor: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """backward of seg_upcat: dy [B,D,H,W,2C] -> (du [B,D/f,H/f,W/f,C] = fp32 sum of the f^3 fine voxels of the first half, rounded once;
+    dskip [B,D,H,W,C] = the second half).  Unsupported arguments (C % 8, factor not 1 / 2, sizes no multiple of it) raise from the ABI."""
+    B, D, H, W, C2 = dy.shape
+    factor = int(factor)
+    assert dy.is_contiguous() and C2 % 2 == 0
+    Cc = C2 // 2
+    f = max(factor, 1)
+    du = torch.empty(B, D // f, H // f, W // f, Cc, device=dy.device, dtype=dy.dtype)
+    dskip = torch.empty(B, D, H, W, Cc, device=dy.device, dtype=dy.dtype)
+    hip.lib().seg_upcat_bwd(_dt(dy), dy.data_ptr(), du.data_ptr(), dskip.data_ptr(), B, D, H, W, Cc, factor, _stream())
+    return du, dskip
+
+
 # ------------------------------------------------------------------ segmentation loss (loss_ops.hip)
 SEG_LOSS_TILE = 256   # AM_SEG_LOSS_TILE
 

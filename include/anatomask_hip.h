@@ -444,6 +444,29 @@ int am_seg_finalize(const float* acc, const float* wsum, int K, int Xp, int Yp, 
 int am_seg_export(const float* acc, const float* wsum, int K, int Xp, int Yp, int Zp, int c0, int c1, int c2, int X, int Y, int Z, int nonlin,
                   const int32_t* region_order, float* probs, void* labels, int label_bytes, void* stream);
 
+/* ---- STUNet segmentation fine-tuning (seg_bwd_ops.hip): the backward of am_seg_head and am_seg_upcat ----
+ * am_seg_head_bwd: one pass over dlogits fp32 [B][K][D][H][W] (class-major: what am_seg_loss_grad writes), with f [B][D][H][W][C] in the
+ * compute dtype and w fp32 [K][C]:
+ *   df [b][v][c]  = sum_k w[k][c] dl[b][k][v]   compute dtype, rounded once; accumulate != 0: df = round(float(df) + that) (a level whose
+ *                                               features feed both its head and the next Upsample_Layer_nearest has two gradient sources)
+ *   dw [k][c]    += sum_{b,v} dl[b][k][v] f[b][v][c]        fp32
+ *   db [k]       += sum_{b,v} dl[b][k][v]                   fp32
+ * All arithmetic is fp32 (the exact fp32 matrix instruction: a k-ordered fmaf chain), as in the forward head.  Any K >= 1 (above 256
+ * classes the launch repeats per 256 classes and df is rounded once per repeat), any C % 8 == 0 (C <= AM_SEG_LDS_C: the tile's features
+ * are staged in LDS; wider: read from global memory), any voxel count.  f and df 16-byte aligned.
+ * dw / db are reduced WITHOUT atomics: a persistent grid of S = min(B ceil(D H W / AM_SEG_HEAD_BWD_TILE), AM_SEG_HEAD_BWD_SLOTS)
+ * workgroups, workgroup s owning tiles s, s + S, ... and the slot s of `workspace` (K C + K floats: its partial dw, db), then an ordered
+ * fold over the slots: the same input gives the same bits.  workspace: at least S (K C + K) floats, uninitialised; workspace_floats is
+ * its size (smaller: -2, nothing is launched). */
+#define AM_SEG_HEAD_BWD_TILE 64
+#define AM_SEG_HEAD_BWD_SLOTS 1024
+int am_seg_head_bwd(int dtype, const float* dlogits, const void* f, const float* w, int B, int D, int H, int W, int C, int K, void* df,
+                    int accumulate, float* dw, float* db, float* workspace, long workspace_floats, void* stream);
+/* Backward of am_seg_upcat: dy [B][D][H][W][2C] -> du [B][D/f][H/f][W/f][C] = the sum over the f^3 fine voxels of dy's first C channels
+ * (fp32, in a fixed order, rounded once) and dskip [B][D][H][W][C] = its second C channels.  f in {1, 2}, D, H, W multiples of f,
+ * C % 8 == 0, 16-byte aligned pointers; anything else returns non-zero and launches nothing. */
+int am_seg_upcat_bwd(int dtype, const void* dy, void* du, void* dskip, int B, int D, int H, int W, int C, int factor, void* stream);
+
 /* ---- segmentation loss: Dice + CE (AM_SEG_SOFTMAX) / Dice + BCE (AM_SEG_SIGMOID) with the logit gradient (loss_ops.hip) ----
  * DC_and_CE_loss / DC_and_BCE_loss around MemoryEfficientSoftDiceLoss (nnunetv2/training/loss/compound_losses.py:8-100, dice.py:58-116,
  * robust_ce_loss.py:6-16) as nnUNetTrainer._build_loss composes them (nnUNetTrainer.py:342-365).
