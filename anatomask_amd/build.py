@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libanatomask_hip.so")
 AB_DIR = os.path.join(os.path.dirname(HERE), "build_ab")      # the tools-only -DAM_ABLATE variant and its objects: never next to the product library
-SOURCES = ["conv_igemm.hip", "conv_k3.hip", "conv_rw.hip", "conv_gather.hip", "conv_wgrad.hip", "conv_wgk3.hip", "stream_ops.hip", "step_ops.hip", "head_ops.hip", "aug_ops.hip", "layer_ops.hip", "seg_ops.hip", "seg_bwd_ops.hip", "loss_ops.hip"]
+SOURCES = ["conv_igemm.hip", "conv_k3.hip", "conv_rw.hip", "conv_gather.hip", "conv_wgrad.hip", "conv_wgk3.hip", "stream_ops.hip", "step_ops.hip", "head_ops.hip", "aug_ops.hip", "layer_ops.hip", "seg_ops.hip", "seg_bwd_ops.hip", "loss_ops.hip", "seg_eval_ops.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-munsafe-fp-atomics", "-Wno-unused-result"]
 
 

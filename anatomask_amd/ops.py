@@ -945,3 +945,51 @@ def seg_loss_grad(mode: int, logits: torch.Tensor, target: torch.Tensor, ignore_
                             int(ignore_label) if (has_ignore and mode == SEG_SOFTMAX) else 0, _p(lse), coef.data_ptr(), gscale.data_ptr(),
                             float(weight), out.data_ptr(), _stream())
     return out
+
+
+# ------------------------------------------------------------------ segmentation validation counts (seg_eval_ops.hip)
+SEG_COUNTS_TILE = 256   # AM_SEG_COUNTS_TILE
+
+
+def seg_hard_counts_workspace_bytes(B: int, n_voxels: int, K: int) -> int:
+    """bytes of am_seg_hard_counts's workspace: one int32 x 4 partial per (sample, tile of SEG_COUNTS_TILE voxels, class)."""
+    return int(B) * ((int(n_voxels) + SEG_COUNTS_TILE - 1) // SEG_COUNTS_TILE) * int(K) * 16
+
+
+def seg_hard_counts(mode: int, logits: torch.Tensor, target: torch.Tensor, ignore_label: Optional[int] = None,
+                    out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
+    """tp / fp / fn of the hard prediction per class, summed over the batch and all voxels: int64 [K, 3], exact, in one pass over the logits
+    (fp32 [B,K,D,H,W] contiguous).  softmax: the prediction is the first index of the maximum (torch.argmax), target int16 labels
+    [B,1,D,H,W], ignore_label (None: none) masks voxels, a label outside [0, K) belongs to no class.  sigmoid: the prediction of region k is
+    x_k > 0, target uint8 / bool [B,K(+1),D,H,W], ignore_label is not None says that its last channel is the ignore mask.  The target is read
+    through its strides.  out (int64 [K,3] on the device): written, or added to with accumulate=True; nothing is read back."""
+    if mode not in (SEG_SOFTMAX, SEG_SIGMOID):
+        raise ValueError(f"mode {mode}: SEG_SOFTMAX or SEG_SIGMOID")
+    if not logits.is_cuda:
+        raise RuntimeError("the segmentation counts run on the GPU only (no CPU path exists)")
+    if logits.dtype != torch.float32 or logits.dim() != 5 or not logits.is_contiguous():
+        raise ValueError(f"logits must be contiguous fp32 [B,K,D,H,W], got {logits.dtype} {tuple(logits.shape)} contiguous={logits.is_contiguous()}")
+    if target.device != logits.device:
+        raise RuntimeError(f"target on {target.device}, logits on {logits.device}")
+    has_ignore = ignore_label is not None
+    B, K, D, H, W = logits.shape
+    if K < 1:
+        raise ValueError("K = 0: at least one class")
+    want_c = 1 if mode == SEG_SOFTMAX else K + (1 if has_ignore else 0)
+    if target.dim() != 5 or tuple(target.shape) != (B, want_c, D, H, W):
+        raise ValueError(f"target {tuple(target.shape)} does not match logits {tuple(logits.shape)}: expected {(B, want_c, D, H, W)}")
+    if mode == SEG_SOFTMAX and target.dtype != torch.int16:
+        raise TypeError(f"softmax mode reads int16 labels, got {target.dtype}")
+    if mode == SEG_SIGMOID and target.dtype not in (torch.uint8, torch.bool):
+        raise TypeError(f"sigmoid mode reads uint8 / bool region channels, got {target.dtype}")
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate needs the table to add to")
+        out = torch.empty(K, 3, device=logits.device, dtype=torch.int64)
+    if out.dtype != torch.int64 or tuple(out.shape) != (K, 3) or not out.is_contiguous() or out.device != logits.device:
+        raise ValueError(f"out must be a contiguous int64 [{K}, 3] tensor on {logits.device}")
+    ws = torch.empty(max(seg_hard_counts_workspace_bytes(B, D * H * W, K), 16), device=logits.device, dtype=torch.uint8)
+    hip.lib().seg_hard_counts(mode, logits.data_ptr(), B, K, D, H, W, target.data_ptr(), *(int(s) for s in target.stride()), int(has_ignore),
+                              int(ignore_label) if (has_ignore and mode == SEG_SOFTMAX) else 0, ws.data_ptr(), ws.numel(), out.data_ptr(),
+                              int(bool(accumulate)), _stream())
+    return out

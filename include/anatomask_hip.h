@@ -502,6 +502,27 @@ int am_seg_loss_grad(int mode, const float* logits, int B, int K, int D, int H, 
                      long tsh, long tsw, int has_ignore, int ignore_label, const float* lse, const float* coef, const float* gscale,
                      float weight, float* dlogits, void* stream);
 
+/* ---- segmentation validation: hard tp / fp / fn counts per class in one pass over the logits (seg_eval_ops.hip) ----
+ * The online evaluation of nnUNetTrainer.validation_step (nnUNetTrainer.py:933-975) with get_tp_fp_fn_tn over axes [0, 2, 3, 4]
+ * (nnunetv2/training/loss/dice.py:150-192).  logits fp32 [B][K][D][H][W] contiguous, the target as am_seg_loss_sums reads it (element
+ * strides; AM_SEG_SOFTMAX int16 labels [B][1][..], AM_SEG_SIGMOID uint8 region channels [B][K (+ 1)][..], channel K the ignore mask when
+ * has_ignore).  With m = the voxel counts (not ignored):
+ *   AM_SEG_SOFTMAX: pred = the FIRST index of the maximum over k (torch.argmax's rule), y = the label:
+ *                   tp_k = #(pred = k, y = k, m), fp_k = #(pred = k, y != k, m), fn_k = #(pred != k, y = k, m).  A label outside [0, K) that
+ *                   is not the ignore label belongs to no class: it adds to fp of the predicted class only.  Any K >= 1.
+ *   AM_SEG_SIGMOID: pred_k = x_k > 0 (sigmoid(x) > 0.5 except for 0 < x < 6e-8, where fp32 sigmoid rounds to 0.5), y_k = the channel:
+ *                   tp_k = #(pred_k, y_k, m), fp_k = #(pred_k, !y_k, m), fn_k = #(!pred_k, y_k, m).
+ * A NaN logit never wins the maximum and is never > 0.  Nothing is indexed by a label or by pred.  All sums are integers (int32 per tile
+ * of AM_SEG_COUNTS_TILE voxels, int64 from there on): exact above 2^24, independent of the order of execution, the same bits on every run.
+ * counts int64 [K][3] = (tp, fp, fn), 8-byte aligned; accumulate != 0 adds to it (a validation epoch leaves one table on the device),
+ * otherwise it is overwritten.  workspace: at least B ceil(D H W / AM_SEG_COUNTS_TILE) K 16 bytes, uninitialised, 16-byte aligned.
+ * Bad arguments (K < 1, an unknown mode, a NULL pointer, a workspace that is too small, misaligned counts / workspace) return -1 and
+ * launch nothing. */
+#define AM_SEG_COUNTS_TILE 256
+int am_seg_hard_counts(int mode, const float* logits, int B, int K, int D, int H, int W, const void* target, long tsb, long tsc, long tsd,
+                       long tsh, long tsw, int has_ignore, int ignore_label, void* workspace, long workspace_bytes, long* counts,
+                       int accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
